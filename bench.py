@@ -51,6 +51,60 @@ def effective_cores() -> int:
     return max(1, n)
 
 
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files together
+DUMP_SAMPLE = 4 << 20          # larger outputs are dumped as a fixed, seeded sample of this many values (16 MB in float32)
+
+
+def flat_sample(total: int, n: int = DUMP_SAMPLE, seed: int = 0):
+    """indices 0 .. total-1, or a fixed, seeded, sorted sample of n of them (numpy int64)"""
+    import numpy as np
+    if total <= n:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, total, n, dtype=np.int64))
+
+
+def param_sample(arena, keys, n: int = DUMP_SAMPLE, seed: int = 0) -> torch.Tensor:
+    """the parameters `keys` of a flat arena (engine.Arena) concatenated in that order, the arena's alignment padding left out --
+    or a fixed, seeded sample of n of those values; the sample does not depend on the arena layout"""
+    import numpy as np
+    starts = np.array([arena.offsets[k][0] for k in keys], dtype=np.int64)
+    sizes = np.array([arena.offsets[k][2] for k in keys], dtype=np.int64)
+    ends = np.cumsum(sizes)
+    logical = flat_sample(int(ends[-1]), n, seed)
+    which = np.searchsorted(ends, logical, side="right")
+    idx = starts[which] + logical - (ends[which] - sizes[which])
+    return arena.p[torch.from_numpy(idx).to(arena.p.device)]
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <out_dir>/<name>.npy, float64 kept, everything else as float32"""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach()
+        host[name] = a.double().cpu().numpy() if a.dtype == torch.float64 else a.float().cpu().numpy()
+    nbytes = sum(a.nbytes for a in host.values())
+    assert nbytes <= DUMP_LIMIT_BYTES, f"--dump-outputs: {nbytes} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] outputs of the last timed step: {', '.join(f'{k}{list(a.shape)}' for k, a in host.items())} -> {out_dir}",
+          file=sys.stderr, flush=True)
+
+
+class LogitsKeepingCrossEntropy:
+    """--dump-outputs: training.FusedCrossEntropy that also keeps a reference to the logits it is given (no copy, no sync), so the
+    logits of the last timed step can be read after the timed region.  Under a HIP graph that is the captured logits buffer, which
+    every replay rewrites."""
+
+    def __init__(self, crit):
+        self.crit, self.weight, self.logits = crit, crit.weight, None
+
+    def __call__(self, logits, labels):
+        self.logits = logits
+        return self.crit(logits, labels)
+
+
 def cpu_baseline(batches=(4, 32), steps=3, seq_len=64, text_model="distilbert", image_model="transformer_B16", image_size=224):
     """The oracle (CPU restatement of the reference's model + run_one_epoch step) on this box's host cores, same synthetic
     tensors, fp32 eager, fine-tuning phase, as SURVEY.md section 8(d) states it: batch 4 (configs[0]'s batch) and batch 32,
@@ -298,6 +352,8 @@ def bench_qformer(args):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "classifier": eng.cls_p})
     # roofline of the dominant kernel family (the bf16 MFMA GEMMs): HIP events around every GEMM launch of a replay
     replay = max(1, min(2, args.steps))
     L.GEMM_PROFILE = []
@@ -496,7 +552,13 @@ def main():
     ap.add_argument("--cross_attention_only", action="store_true", help="configs[3]: ViT-L/16 + BERT-base, --seq_len 128")
     ap.add_argument("--workload", default="mmrca", choices=("mmrca", "qformer"),
                     help="mmrca: the headline MM-RCA train step | qformer: BASELINE configs[4], the BLIP-2 Q-Former classifier iteration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): mmrca -- loss, logits [batch, 4], "
+                         "params (the parameters after the optimizer step, in state_dict order; a fixed, seeded sample of 4 Mi values when there "
+                         "are more), bn_buffers (conv backbones: BatchNorm running statistics, likewise); qformer -- loss, classifier")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # no launcher: be one (before anything below touches the GPU)
         sys.exit(launch_ranks(args.gpus))
     if args.workload == "qformer":
@@ -531,6 +593,8 @@ def main():
             p.requires_grad = True
     opt = FlatSGD(model, lr=1e-3, weight_decay=1e-2)
     crit = FusedCrossEntropy(None, 0.0)
+    if args.dump_outputs:
+        crit = LogitsKeepingCrossEntropy(crit)
     sync = D.GradSync(model.engine.arena.g, world) if world > 1 else None
     comm = None
     if world > 1:
@@ -602,6 +666,14 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:        # before the untimed steps below move the parameters on
+        eng = model.engine
+        outs = {"loss": loss, "logits": crit.logits, "params": param_sample(eng.arena, eng.param_keys)}
+        if eng.conv is not None:
+            stats = [t.reshape(-1) for k, t in sorted(eng.conv.buffers.items()) if not k.endswith("num_batches_tracked")]
+            stats = torch.cat(stats)
+            outs["bn_buffers"] = stats[torch.from_numpy(flat_sample(stats.numel())).to(dev)]
+        dump_outputs(args.dump_outputs, outs)
     if world > 1:
         sync.timing = False
         wait_ms = sum(e0.elapsed_time(e1) for e0, e1 in sync.wait_events)

@@ -865,6 +865,30 @@ def test_bench_launches_its_own_ranks_and_reports_a_failed_one(tmp_path, capfd):
     assert time.time() - t0 < 60                  # rank 0 (sleeping) was ended, not waited for
 
 
+def test_bench_output_dump_samples_parameters_in_state_dict_order(tmp_path):
+    """bench.py --dump-outputs: the parameter values are the arena's entries in key order without its alignment padding, or a
+    fixed, seeded sample of them; the files are float32 (float64 kept) and stay under the size limit"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from garbage_classification_rca_amd.engine import Arena
+    ents = [("a", (3, 5)), ("b", (7,)), ("c", (2, 2, 2))]
+    ar = Arena(ents, "cpu", with_lp=False)
+    for k, _ in ents:
+        ar.view(k).copy_(torch.randn(ar.view(k).shape))
+    flat = torch.cat([ar.view(k).reshape(-1) for k, _ in ents])
+    assert ar.total > flat.numel()                                     # (there is padding to leave out)
+    assert torch.equal(bench.param_sample(ar, [k for k, _ in ents]), flat)
+    s1, s2 = (bench.param_sample(ar, [k for k, _ in ents], n=16, seed=3) for _ in range(2))
+    assert torch.equal(s1, s2) and s1.numel() == 16
+    assert torch.equal(s1, flat[torch.from_numpy(bench.flat_sample(flat.numel(), 16, 3))])
+    bench.dump_outputs(str(tmp_path / "d"), {"x": flat.bfloat16(), "y": flat.double(), "loss": torch.ones(1)})
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("x", "y", "loss")}
+    assert got["x"].dtype == np.float32 and got["y"].dtype == np.float64 and got["loss"].dtype == np.float32
+    assert np.array_equal(got["y"], flat.double().numpy())
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+
+
 def _width_worker(rank, world, port, q):
     """two ranks whose batches use different caption widths end up on the SAME trimmed width (the graph key of a captured train step)"""
     import torch.distributed as dist
