@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/mmrca.h"
 
 typedef __bf16 bf16_t;
@@ -77,6 +78,27 @@ static inline void mmrca_max_lds(const void* fn, int bytes, MmrcaLdsAttr& c) {
     static MmrcaLdsAttr mmrca_lds_attr_;                                         \
     mmrca_max_lds((const void*)(__VA_ARGS__), (int)(bytes), mmrca_lds_attr_);    \
   } while (0)
+
+// CUs of the current device as the GEMM dispatch counts them: rounded down to a multiple of 8 (whole XCDs), 256 when the query
+// fails or reports fewer than 8.  Read once per translation unit.
+static inline int cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0, c = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 8) c = 256;
+    n = c & ~7;
+  }
+  return n;
+}
+
+// with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...): runtime flags (operand layouts,
+// accumulate mode, ...) become template arguments, one instantiation per combination, without a hand-written if / else ladder.
+template <class F> static inline void with_bools(F&& f) { f(); }
+template <class F, class... Bs> static inline void with_bools(F&& f, bool b, Bs... rest) {
+  if (b) with_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
+  else with_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
+}
 
 // Step epoch of the counter-based masks.  Every launch carries its mask seed BY VALUE, so a launch captured in a HIP graph
 // (training.GraphedTrainStep) would redraw the captured step's masks at every replay.  The hash therefore runs on

@@ -24,7 +24,6 @@
 //   * gemm256.hip   : the persistent 256x256 kernel that runs the encoder-sized GEMMs (the headline K2 number).
 #include "common.h"
 #include "lds_asm.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
@@ -1274,6 +1273,18 @@ static void launch_mfma1s(const void* A, const void* B, void* C, const void* bia
                      (bf16_t*)C_lo, nseg, bst, pre16);
 }
 
+// Weight-gradient K split (accumulate mode, fp32 atomics): `target` resident block slots over `tiles` output tiles, at least four
+// K steps per range.
+static void wgrad_ksplit(int64_t K, int64_t tiles, int64_t target, int& ksplits, int64_t& ksplit_len) {
+  const int64_t ksteps = K / GBK;
+  int64_t want = target / tiles;
+  if (want < 1) want = 1;
+  if (want > ksteps / 4) want = ksteps / 4 > 0 ? ksteps / 4 : 1;
+  const int64_t steps_per = (ksteps + want - 1) / want;
+  ksplit_len = steps_per * GBK;
+  ksplits = (int)((ksteps + steps_per - 1) / steps_per);
+}
+
 // entry used by gemm_x3.hip: the single-stage 128x128 kernel in its bf16x3 form (any epilogue; accumulate mode = fp32 atomics)
 int mmrca_gemm_k1s_x3(const void* A_hi, const void* A_lo, const void* B_hi, const void* B_lo, void* C, void* C_lo, const void* bias,
                       const void* addend, void* preact, float* colsum, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
@@ -1281,38 +1292,21 @@ int mmrca_gemm_k1s_x3(const void* A_hi, const void* A_lo, const void* B_hi, cons
   const int tiles_m = (int)((M + GBM - 1) / GBM), tiles_n = (int)(N / GBN);
   int ksplits = 1;
   int64_t ksplit_len = K;
-  if (accum) {
-    const int64_t ksteps = K / GBK;
-    int64_t want = 1024 / ((int64_t)tiles_m * tiles_n);
-    if (want < 1) want = 1;
-    if (want > ksteps / 4) want = ksteps / 4 > 0 ? ksteps / 4 : 1;
-    const int64_t steps_per = (ksteps + want - 1) / want;
-    ksplit_len = steps_per * GBK;
-    ksplits = (int)((ksteps + steps_per - 1) / steps_per);
-  }
+  if (accum) wgrad_ksplit(K, (int64_t)tiles_m * tiles_n, 1024, ksplits, ksplit_len);
   const bool ak = a_layout == MMRCA_KROW, bk = b_layout == MMRCA_KROW, at = accum != 0;
-  // the fused four-plane form: all three plane pairs, an epilogue (no accumulate mode), K % 32 == 0 (MMRCA_X3_FUSED_K1S=0: the three-pass loop)
-  static const int fused_k1s = getenv("MMRCA_X3_FUSED_K1S") ? atoi(getenv("MMRCA_X3_FUSED_K1S")) : 1;
-  if (fused_k1s && A_lo && B_lo && !at && K % 32 == 0) {
-#define L1SF(AK_, BK_) launch_mfma1s<AK_, BK_, false, 4, true, false, true>(A_hi, B_hi, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, 1, K, colsum, st, A_lo, B_lo, C_lo, 3, BnStat{nullptr, nullptr, nullptr}, pre16)
-    if (!ak && !bk) L1SF(false, false);
-    else if (!ak && bk) L1SF(false, true);
-    else if (ak && !bk) L1SF(true, false);
-    else L1SF(true, true);
-#undef L1SF
+  // the fused four-plane form: all three plane pairs, an epilogue (no accumulate mode), K % 32 == 0
+  if (A_lo && B_lo && !at && K % 32 == 0) {
+    with_bools([&](auto ak_, auto bk_) {
+      launch_mfma1s<ak_, bk_, false, 4, true, false, true>(A_hi, B_hi, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, 1, K,
+                                                           colsum, st, A_lo, B_lo, C_lo, 3, BnStat{nullptr, nullptr, nullptr}, pre16);
+    }, ak, bk);
     MMRCA_CHECK_LAUNCH("gemm_x3(k1s,fused)");
     return 0;
   }
-#define L1SX(AK_, BK_, AT_) launch_mfma1s<AK_, BK_, AT_, 4, true>(A_hi, B_hi, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, colsum, st, A_lo, B_lo, C_lo, A_lo ? (B_lo ? 3 : 2) : 1, BnStat{nullptr, nullptr, nullptr}, pre16)
-  if (!ak && !bk && !at) L1SX(false, false, false);
-  else if (!ak && bk && !at) L1SX(false, true, false);
-  else if (ak && !bk && !at) L1SX(true, false, false);
-  else if (ak && bk && !at) L1SX(true, true, false);
-  else if (!ak && !bk && at) L1SX(false, false, true);
-  else if (!ak && bk && at) L1SX(false, true, true);
-  else if (ak && !bk && at) L1SX(true, false, true);
-  else L1SX(true, true, true);
-#undef L1SX
+  with_bools([&](auto ak_, auto bk_, auto at_) {
+    launch_mfma1s<ak_, bk_, at_, 4, true>(A_hi, B_hi, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len,
+                                          colsum, st, A_lo, B_lo, C_lo, A_lo ? (B_lo ? 3 : 2) : 1, BnStat{nullptr, nullptr, nullptr}, pre16);
+  }, ak, bk, at);
   MMRCA_CHECK_LAUNCH("gemm_x3(k1s)");
   return 0;
 }
@@ -1325,11 +1319,8 @@ int mmrca_gemm256(const void* A, const void* B, void* C, const void* bias, const
                   float* colsum, hipStream_t st);
 
 int mmrca_gemm256_streamk_split(int64_t M, int64_t N, int64_t ksteps, void* stream, bool x3);
+int64_t mmrca_gemm256_round_split(int64_t M, int64_t N);
 extern int g_mmrca_dbg;
-static const int g_mmrca_auto256_side = getenv("MMRCA_AUTO256_SIDE") ? atoi(getenv("MMRCA_AUTO256_SIDE")) : 0;
-static const bool g_mmrca_auto256_gelu = getenv("MMRCA_AUTO256_GELU") ? atoi(getenv("MMRCA_AUTO256_GELU")) != 0 : true;
-static const int g_mmrca_auto256_tail = getenv("MMRCA_AUTO256_TAIL") ? atoi(getenv("MMRCA_AUTO256_TAIL")) : 2;
-static const int g_mmrca_auto256_tail_pct = getenv("MMRCA_AUTO256_TAIL_PCT") ? atoi(getenv("MMRCA_AUTO256_TAIL_PCT")) : 60;
 
 template <bool AK, bool BK2, bool AT, bool DB>
 static void launch_mfma(const void* A, const void* B, void* C, const void* bias, const void* addend, void* preact,
@@ -1365,13 +1356,11 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* bias
   // 128; contraction a multiple of 32, not of 64): edge tiles stage a clamped (duplicate) chunk and never store it, the 32-deep
   // kernel takes the odd half K step.  Plain epilogue only (bias allowed): side operands are read per tile and would run
   // past the last row.  These shapes used to fall to the general kernel at a fifth of the rate.
-  static const bool ragged_on = !(getenv("MMRCA_GEMM_RAGGED") && atoi(getenv("MMRCA_GEMM_RAGGED")) == 0);
   const bool strict_mfma = ok_mfma;
   // (round 5: a contraction that is a multiple of 8 but not of 32 -- EfficientNetV2-M's 80 / 176 / 304 channels -- is taken by the
-  // 32-deep kernel's edge step; forward / input gradient only, MMRCA_GEMM_KEDGE=0 restores the general kernel for them)
-  static const bool kedge_on = !(getenv("MMRCA_GEMM_KEDGE") && atoi(getenv("MMRCA_GEMM_KEDGE")) == 0);
-  const bool k_ok = K % 32 == 0 || (kedge_on && !out_f32_accum && K % 8 == 0 && K >= 32);
-  if (!ok_mfma && ragged_on && dtype == MMRCA_BF16 && N % 8 == 0 && N >= 8 && k_ok && (a_layout == MMRCA_ROWK || (M % 8 == 0 && M >= 8)) &&
+  // 32-deep kernel's edge step; forward / input gradient only)
+  const bool k_ok = K % 32 == 0 || (!out_f32_accum && K % 8 == 0 && K >= 32);
+  if (!ok_mfma && dtype == MMRCA_BF16 && N % 8 == 0 && N >= 8 && k_ok && (a_layout == MMRCA_ROWK || (M % 8 == 0 && M >= 8)) &&
       lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 && aligned16(A) && aligned16(B) && aligned16(C) && (!bias || (aligned16(bias) && !out_f32_accum)) &&
       !addend && !preact && act == MMRCA_ACT_NONE && !colsum_fused && (out_f32_accum ? K % 64 == 0 : true) && M >= (out_f32_accum ? 16 : 64) &&
       (impl == MMRCA_GEMM_AUTO || impl == MMRCA_GEMM_MFMA_BK32 || impl == MMRCA_GEMM_MFMA_1STAGE))
@@ -1390,40 +1379,23 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* bias
   // AUTO (tools/gemm_bench.py, interleaved rounds, round 2): the persistent 256x256 kernel (operand stream in flight across
   // barriers and tile boundaries, barrier-free epilogue) wins on every bias-only shape once there is a full round of tiles:
   // K = 768: 870-1,120 vs 830-910 TFLOP/s for the 128x128 single-stage kernel, K >= 2304: 1,010-1,070 vs 910-920.
-  // Epilogues with a side operand (residual addend, gelu' factor) are not built there and stay on the 128x128 kernel.
-  const bool side256 = addend != nullptr || act == MMRCA_ACT_MUL;     // epilogues with a side operand: MMRCA_AUTO256_SIDE bit 0 = addend at K >= 1536, bit 1 = MUL, bit 2 = addend at any K
-  const bool side_ok = !side256 || (addend != nullptr && act == MMRCA_ACT_NONE && (((g_mmrca_auto256_side & 1) && K >= 1536) || (g_mmrca_auto256_side & 4))) ||
-                       (act == MMRCA_ACT_MUL && (g_mmrca_auto256_side & 2));
-  const bool auto256 = impl == MMRCA_GEMM_AUTO && ok256 && M % 256 == 0 && K >= 768 && (M / 256) * (N / 256) >= 256 && side_ok &&
-                       (act != MMRCA_ACT_GELU_SAVE_GRAD || g_mmrca_auto256_gelu);
+  // Epilogues with a side operand (residual addend, gelu' factor) stay on the 128x128 kernel.
+  const bool side256 = addend != nullptr || act == MMRCA_ACT_MUL;
+  const bool auto256 = impl == MMRCA_GEMM_AUTO && ok256 && M % 256 == 0 && K >= 768 && (M / 256) * (N / 256) >= 256 && !side256;
   if (ok256 && (impl == MMRCA_GEMM_MFMA256 || auto256)) {
-    // Tile quantisation: the persistent kernel runs whole rounds of one 256x256 tile per CU.  N = 768 at M = 50,432 makes
-    // 591 tiles = 2.31 rounds on 256 CUs, i.e. the chip idles for 0.69 of a round.  AUTO gives the persistent kernel the
-    // leading row blocks that make whole rounds and hands the remaining rows to the 128x128 kernel (MMRCA_AUTO256_TAIL:
-    // 0 = off, 1 = single-stage kernel, 2 = two-stage kernel for the tail (default); only when the partial round is 25-60 % of a
-    // round).  Isolated: FFN2 forward 223 -> 209 us, QKV input gradient 179 -> 160, FFN1 input gradient 233 -> 218.
+    // AUTO splits a launch with a partial round (mmrca_gemm256_round_split) and hands the remaining rows to the two-stage 128x128
+    // kernel.  Isolated: FFN2 forward 223 -> 209 us, QKV input gradient 179 -> 160, FFN1 input gradient 233 -> 218.
     // Round 6: with a stream-K workspace registered for the stream (mmrca_gemm_streamk_workspace) the partial round stays INSIDE
-    // the persistent launch -- the leftover tiles' K loops are cut into ranges across all CUs (gemm256.hip) -- and the split below
-    // is not taken.
-    const bool sk_tail = mmrca_gemm256_streamk_split(M, N, K / 64, stream, false) >= 2;
-    if (auto256 && !sk_tail && g_mmrca_auto256_tail > 0 && !colsum_fused && a_layout == MMRCA_ROWK) {
-      int ncu = 256, devi = 0;
-      (void)hipGetDevice(&devi);
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devi) != hipSuccess || ncu < 8) ncu = 256;
-      ncu &= ~7;
-      const int64_t tm = M / 256, tn = N / 256, tiles = tm * tn;
-      const int64_t rounds = tiles / ncu, rem = tiles - rounds * ncu;
-      const int64_t m_split = rounds * ncu / tn;                  // row blocks of the whole rounds
-      if (rounds >= 1 && rem * 100 >= 25 * (int64_t)ncu && rem * 100 < (int64_t)g_mmrca_auto256_tail_pct * ncu && m_split >= 1 && m_split < tm) {
-        const int64_t M1 = m_split * 256;
-        if (int rc = mmrca_gemm256(A, B, C, bias, addend, preact, M1, N, K, lda, ldb, ldc, a_layout, b_layout, act, nullptr, st)) return rc;
-        const char* A2 = (const char*)A + M1 * lda * 2;
-        char* C2 = (char*)C + M1 * ldc * 2;
-        const char* add2 = addend ? (const char*)addend + M1 * ldc * 2 : nullptr;
-        char* pre2 = preact ? (char*)preact + M1 * ldc * 2 : nullptr;
-        return gemm_dispatch(A2, B, C2, bias, add2, pre2, M - M1, N, K, lda, ldb, ldc, a_layout, b_layout, act, 0, dtype,
-                             g_mmrca_auto256_tail == 2 ? MMRCA_GEMM_MFMA : MMRCA_GEMM_MFMA_1STAGE, stream, nullptr, nullptr);
-      }
+    // the persistent launch -- the leftover tiles' K loops are cut into ranges across all CUs (gemm256.hip) -- and there is no split.
+    const int64_t M1 = auto256 && !colsum_fused && mmrca_gemm256_streamk_split(M, N, K / 64, stream, false) < 2 ? mmrca_gemm256_round_split(M, N) : 0;
+    if (M1 > 0) {
+      if (int rc = mmrca_gemm256(A, B, C, bias, addend, preact, M1, N, K, lda, ldb, ldc, a_layout, b_layout, act, nullptr, st)) return rc;
+      const char* A2 = (const char*)A + M1 * lda * 2;
+      char* C2 = (char*)C + M1 * ldc * 2;
+      const char* add2 = addend ? (const char*)addend + M1 * ldc * 2 : nullptr;
+      char* pre2 = preact ? (char*)preact + M1 * ldc * 2 : nullptr;
+      return gemm_dispatch(A2, B, C2, bias, add2, pre2, M - M1, N, K, lda, ldb, ldc, a_layout, b_layout, act, 0, dtype, MMRCA_GEMM_MFMA,
+                           stream, nullptr, nullptr);
     }
     if (colsum_fused && fused_done) *fused_done = true;
     return mmrca_gemm256(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, a_layout, b_layout, act, colsum_fused, st);
@@ -1439,15 +1411,10 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* bias
     int ksplits = 1;
     int64_t ksplit_len = K;
     if (out_f32_accum) {
-      const int64_t ksteps = K / GBK;
-      // resident slots = 256 CUs x 2 blocks: aim for one (few tiles) or two (many tiles) full rounds
-      const int64_t target = (g_mmrca_dbg >> 8) > 0 ? (g_mmrca_dbg >> 8) : ((int64_t)tiles_m * tiles_n >= 64 ? 1024 : 512);   // see below: 1024 = one round of 4 blocks/CU (BK=32 kernel) or two rounds of 2 (BK=64)
-      int64_t want = target / ((int64_t)tiles_m * tiles_n);
-      if (want < 1) want = 1;
-      if (want > ksteps / 4) want = ksteps / 4 > 0 ? ksteps / 4 : 1;
-      const int64_t steps_per = (ksteps + want - 1) / want;
-      ksplit_len = steps_per * GBK;
-      ksplits = (int)((ksteps + steps_per - 1) / steps_per);
+      // resident slots = 256 CUs x 2 blocks: aim for one (few tiles) or two (many tiles) full rounds.  1024 = one round of 4
+      // blocks/CU (BK=32 kernel) or two rounds of 2 (BK=64); g_mmrca_dbg >> 8 overrides it (tools/gemm_bench.py)
+      const int64_t tiles = (int64_t)tiles_m * tiles_n;
+      wgrad_ksplit(K, tiles, (g_mmrca_dbg >> 8) > 0 ? (g_mmrca_dbg >> 8) : (tiles >= 64 ? 1024 : 512), ksplits, ksplit_len);
     }
     const bool ak = a_layout == MMRCA_KROW, bk = b_layout == MMRCA_KROW, at = out_f32_accum != 0;
     // AUTO (tools/gemm_bench.py, interleaved A/B on the encoder shapes): thread-level parallelism beats software prefetch on
@@ -1456,30 +1423,20 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* bias
     //     kernel at two blocks per CU); 64-deep steps keep the ROWK operands' HBM reads in full 128-byte lines;
     //   wgrad (KROW,KROW, fp32 atomics): two-stage 128x128x32 (800-870 vs 680-740), unless there are too few tiles.
     // ragged contraction (K % 64 != 0): the 32-deep kernel takes K % 32 == 0 exactly and anything else through its edge step.  The
-    // single-stage 64-deep kernel has the same edge step (MMRCA_GEMM_KEDGE64=1 sends forward / input gradient AUTO launches with
-    // K % 64 != 0 there: longer steps, half the barriers per flop) -- measured neutral on both conv workloads (EfficientNetV2-M 909.4 vs
-    // 906.9 samples/s, configs[2] 627.1 vs 626.9: these products wait on HBM, not on barriers), so it is off by default.
-    static const int kedge64 = getenv("MMRCA_GEMM_KEDGE64") ? atoi(getenv("MMRCA_GEMM_KEDGE64")) : 0;
-    const bool edge64 = kedge_on && ((kedge64 && impl == MMRCA_GEMM_AUTO) || impl == MMRCA_GEMM_MFMA_1STAGE) && !out_f32_accum && K % 64 != 0 &&
-                        K % 8 == 0 && K >= 64;      // (an explicit MFMA_1STAGE request always gets it: the tests do that)
+    // single-stage 64-deep kernel has the same edge step; AUTO does not use it there (measured neutral on both conv workloads:
+    // EfficientNetV2-M 909.4 vs 906.9 samples/s, configs[2] 627.1 vs 626.9 -- these products wait on HBM, not on barriers), an
+    // explicit MFMA_1STAGE request gets it (the tests do that).
+    const bool edge64 = impl == MMRCA_GEMM_MFMA_1STAGE && !out_f32_accum && K % 64 != 0 && K % 8 == 0 && K >= 64;
     const bool need32 = K % 64 != 0 && !edge64;
-    // (experiment, round 4: below this many 128x128 tiles -- an under-filled chip, where the single-stage kernel has no sibling blocks to
-    // hide its load -> barrier -> compute sequence -- AUTO takes the two-stage kernel; 0 = never.  Result in DESIGN K2.)
-    static const int g_auto_2stage_below = getenv("MMRCA_AUTO_2STAGE_BELOW") ? atoi(getenv("MMRCA_AUTO_2STAGE_BELOW")) : 512;
+    // (round 4: below 512 128x128 tiles -- an under-filled chip, where the single-stage kernel has no sibling blocks to hide its
+    // load -> barrier -> compute sequence -- AUTO takes the two-stage kernel.  Result in DESIGN K2.)
     const bool auto1s = impl == MMRCA_GEMM_AUTO && !at && !need32 &&
-                        (edge64 || !((int64_t)tiles_m * tiles_n < g_auto_2stage_below && K >= 768 && !colsum_fused && !ragged));
+                        !((int64_t)tiles_m * tiles_n < 512 && K >= 768 && !colsum_fused && !ragged);
     const bool auto32 = (impl == MMRCA_GEMM_AUTO && at && (int64_t)tiles_m * tiles_n >= 64) || need32;
     if ((impl == MMRCA_GEMM_MFMA_BK32 || auto32) && !(at && bias)) {
-#define L32(AK_, BK_, AT_) launch_mfma32<AK_, BK_, AT_>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, st)
-      if (!ak && !bk && !at) L32(false, false, false);
-      else if (!ak && bk && !at) L32(false, true, false);
-      else if (ak && !bk && !at) L32(true, false, false);
-      else if (ak && bk && !at) L32(true, true, false);
-      else if (!ak && !bk && at) L32(false, false, true);
-      else if (!ak && bk && at) L32(false, true, true);
-      else if (ak && !bk && at) L32(true, false, true);
-      else L32(true, true, true);
-#undef L32
+      with_bools([&](auto ak_, auto bk_, auto at_) {
+        launch_mfma32<ak_, bk_, at_>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, st);
+      }, ak, bk, at);
       MMRCA_CHECK_LAUNCH("gemm(mfma,bk32)");
       return 0;
     }
@@ -1487,41 +1444,29 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* bias
     if ((impl == MMRCA_GEMM_MFMA_1STAGE || auto1s) && !(at && bias)) {
       float* cs1 = at ? nullptr : colsum_fused;
       if (cs1 && fused_done) *fused_done = true;
-#define L1S(AK_, BK_, AT_) launch_mfma1s<AK_, BK_, AT_, 4>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, cs1, st)
-      if (!ak && !bk && !at) L1S(false, false, false);
-      else if (!ak && bk && !at) L1S(false, true, false);
-      else if (ak && !bk && !at) L1S(true, false, false);
-      else if (ak && bk && !at) L1S(true, true, false);
-      else if (!ak && !bk && at) L1S(false, false, true);
-      else if (!ak && bk && at) L1S(false, true, true);
-      else if (ak && !bk && at) L1S(true, false, true);
-      else L1S(true, true, true);
-#undef L1S
+      with_bools([&](auto ak_, auto bk_, auto at_) {
+        launch_mfma1s<ak_, bk_, at_, 4>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, cs1, st);
+      }, ak, bk, at);
       MMRCA_CHECK_LAUNCH("gemm(mfma,1stage)");
       return 0;
     }
     if (at && bias && (impl == MMRCA_GEMM_MFMA_BK32 || auto32)) {   // the same on the 128x128x32 kernel (four blocks per CU)
-      if (bk) launch_mfma32<true, true, true, true>(A, B, C, nullptr, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, st, (float*)bias);
-      else launch_mfma32<true, false, true, true>(A, B, C, nullptr, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, st, (float*)bias);
+      with_bools([&](auto bk_) {
+        launch_mfma32<true, bk_, true, true>(A, B, C, nullptr, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, st, (float*)bias);
+      }, bk);
       MMRCA_CHECK_LAUNCH("gemm(mfma,bk32,wgrad+dbias)");
       return 0;
     }
     if (at && bias) {   // weight gradient with the bias gradient fused (A is KROW by contract)
-      if (bk) launch_mfma<true, true, true, true>(A, B, C, nullptr, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, (float*)bias, st);
-      else launch_mfma<true, false, true, true>(A, B, C, nullptr, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, (float*)bias, st);
+      with_bools([&](auto bk_) {
+        launch_mfma<true, bk_, true, true>(A, B, C, nullptr, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, (float*)bias, st);
+      }, bk);
       MMRCA_CHECK_LAUNCH("gemm(mfma,wgrad+dbias)");
       return 0;
     }
-#define L(AK_, BK_, AT_) launch_mfma<AK_, BK_, AT_, false>(A, B, C, out_f32_accum ? nullptr : bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, out_f32_accum ? (float*)bias : nullptr, st)
-    if (!ak && !bk && !at) L(false, false, false);
-    else if (!ak && bk && !at) L(false, true, false);
-    else if (ak && !bk && !at) L(true, false, false);
-    else if (ak && bk && !at) L(true, true, false);
-    else if (!ak && !bk && at) L(false, false, true);
-    else if (!ak && bk && at) L(false, true, true);
-    else if (ak && !bk && at) L(true, false, true);
-    else L(true, true, true);
-#undef L
+    with_bools([&](auto ak_, auto bk_, auto at_) {     // (a bias here is never a bias gradient: that case returned above)
+      launch_mfma<ak_, bk_, at_, false>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, act, tiles_m, tiles_n, ksplits, ksplit_len, nullptr, st);
+    }, ak, bk, at);
     MMRCA_CHECK_LAUNCH("gemm(mfma)");
     return 0;
   }
@@ -1532,9 +1477,8 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* bias
   }
   const int64_t sam = a_layout == MMRCA_ROWK ? lda : 1, sak = a_layout == MMRCA_ROWK ? 1 : lda;
   const int64_t sbn = b_layout == MMRCA_ROWK ? ldb : 1, sbk = b_layout == MMRCA_ROWK ? 1 : ldb;
-  // AUTO: the fp32-matrix-core kernel; impl == REF (or MMRCA_GEMM_GEN=0): the VALU reference kernel
-  static const bool gen_on = !(getenv("MMRCA_GEMM_GEN") && atoi(getenv("MMRCA_GEMM_GEN")) == 0);
-  if (impl != MMRCA_GEMM_REF && gen_on) {
+  // AUTO: the fp32-matrix-core kernel; impl == REF: the VALU reference kernel
+  if (impl != MMRCA_GEMM_REF) {
     const int64_t tm = (M + 127) / 128, tn = (N + 63) / 64;
     MMRCA_REQUIRE(tm * tn < (1ll << 31), "gemm(gen): too many tiles");
     int64_t splits = 1, ksplit_len = K;

@@ -32,7 +32,6 @@
 //   2,0,0,0.
 #include "common.h"
 #include "lds_asm.h"
-#include <stdlib.h>
 #include <type_traits>
 #include <mutex>
 
@@ -789,8 +788,6 @@ gemm_p256_k(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, bf16_t* 
 }
 
 extern int g_mmrca_dbg;
-static int g_num_cus = 0;
-static int g_p256_skew = -1;      // x 10 ns between the four start groups (MMRCA_P256_SKEW; see gemm_p256_k)
 
 // ---- stream-K tail workspaces: caller-owned, one per stream that launches GEMMs (mmrca_gemm_streamk_workspace, include/mmrca.h)
 #define SK_COUNTER_BYTES 4096          // 1,024 tile counters (at most 255 are used), zero between launches
@@ -812,8 +809,7 @@ extern "C" int mmrca_gemm_streamk_workspace(void* workspace, int64_t bytes, void
       else g_sk_ws[i] = g_sk_ws[--g_sk_ws_n];
       return 0;
     }
-  if (!workspace) return 0;
-  MMRCA_REQUIRE(g_sk_ws_n < 32, "gemm_streamk_workspace: more than 32 (device, stream) pairs registered");
+  if (!workspace || g_sk_ws_n == 32) return 0;     // registry full: this stream runs without the tail
   g_sk_ws[g_sk_ws_n++] = SkWorkspace{dev, stream, (char*)workspace, bytes};
   return 0;
 }
@@ -826,41 +822,26 @@ static char* sk_workspace_of(void* stream) {
     if (g_sk_ws[i].stream == stream && g_sk_ws[i].device == dev) return g_sk_ws[i].base;
   return nullptr;
 }
-static int num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    g_num_cus = n & ~7;
-  }
-  return g_num_cus;
-}
 // how many K ranges the leftover tiles of a launch are cut into (0 / 1 = no stream-K tail): as many as fill the chip once,
-// each at least two K steps long (the stream's pipeline), at most MMRCA_SK_MAX (default 4: the unit that finishes a tile reads
-// all its partials, 256 KiB each, on ONE CU).  No workspace registered for the stream = no tail.
-static int g_sk_max = -1, g_sk_min_ksteps = -1, g_sk_bf16 = -1;
-static void sk_config_init() {
-  // plain bf16 products: measured neutral at K >= 1536 and slower below (profiles/r06_streamk_ab.txt) -> off unless asked for;
-  // the fused bf16x3 form does three times the matrix work per tile for the same partial-tile traffic: +1.3 % on the compliant step
-  if (g_sk_bf16 < 0) g_sk_bf16 = getenv("MMRCA_SK_BF16") ? atoi(getenv("MMRCA_SK_BF16")) : 0;
-  if (g_sk_max < 0) g_sk_max = getenv("MMRCA_SK_MAX") ? atoi(getenv("MMRCA_SK_MAX")) : 4;
-  // (the partial tiles are 2 x 256 KiB of HBM traffic per unit whatever K is: below this many K steps the round-5 split -- whole
-  // rounds here, the rest on the 128x128 kernel -- is faster; tools/streamk_bench.py, profiles/r06_streamk_ab.txt)
-  if (g_sk_min_ksteps < 0) g_sk_min_ksteps = getenv("MMRCA_SK_MIN_KSTEPS") ? atoi(getenv("MMRCA_SK_MIN_KSTEPS")) : 24;
-}
+// each at least two K steps long (the stream's pipeline), at most g_sk_max (the unit that finishes a tile reads all its partials,
+// 256 KiB each, on ONE CU).  No workspace registered for the stream = no tail.  mmrca_gemm_streamk_config changes the limits.
+// Plain bf16 products: measured neutral at K >= 1536 and slower below (profiles/r06_streamk_ab.txt) -> off; the fused bf16x3 form
+// does three times the matrix work per tile for the same partial-tile traffic: +1.3 % on the compliant step.
+// (The partial tiles are 2 x 256 KiB of HBM traffic per unit whatever K is: below g_sk_min_ksteps K steps the round-5 split --
+// whole rounds here, the rest on the 128x128 kernel -- is faster; tools/streamk_bench.py, profiles/r06_streamk_ab.txt.)
+static int g_sk_max = 4, g_sk_min_ksteps = 24;
+static bool g_sk_bf16 = false;
 extern "C" int mmrca_gemm_streamk_config(int max_split, int min_ksteps, int bf16_products) {
-  sk_config_init();
   if (max_split >= 0) g_sk_max = max_split;
   if (min_ksteps >= 0) g_sk_min_ksteps = min_ksteps;
-  if (bf16_products >= 0) g_sk_bf16 = bf16_products;
+  if (bf16_products >= 0) g_sk_bf16 = bf16_products != 0;
   return 0;
 }
 int mmrca_gemm256_streamk_split(int64_t M, int64_t N, int64_t ksteps, void* stream, bool x3) {
-  sk_config_init();
   const int sk_max = g_sk_max;
   if ((!x3 && !g_sk_bf16) || ksteps < g_sk_min_ksteps || !sk_workspace_of(stream)) return 0;
   const int64_t tiles = ((M + 255) / 256) * (N / 256);
-  const int ncu = num_cus();
+  const int ncu = cu_count();
   if (tiles < ncu) return 0;             // (fewer tiles than CUs, ranges over the whole chip: measured slower than the 128x128 kernels,
                                          //  profiles/r06_text_gemm_shapes.txt)
   const int64_t left = tiles % ncu;
@@ -870,17 +851,24 @@ int mmrca_gemm256_streamk_split(int64_t M, int64_t N, int64_t ksteps, void* stre
   if (split > sk_max) split = sk_max;
   return split >= 2 ? (int)split : 0;
 }
+// Tile quantisation: the persistent kernel runs whole rounds of one 256x256 tile per CU.  N = 768 at M = 50,432 makes 591 tiles =
+// 2.31 rounds on 256 CUs, i.e. the chip idles for 0.69 of a round.  AUTO (mmrca_gemm, mmrca_gemm_x3) gives the persistent kernel
+// the leading row blocks that make whole rounds and hands the remaining rows to a 128x128 kernel when the partial round is 25-60 %
+// of a round (upper bounds of 0 / 30 / 60 % measured within noise, profiles/README.md).  Returns the rows of the whole rounds, or 0 = no
+// split.  M and N are multiples of 256.
+int64_t mmrca_gemm256_round_split(int64_t M, int64_t N) {
+  const int64_t ncu = cu_count(), tm = M / 256, tn = N / 256, tiles = tm * tn;
+  const int64_t rounds = tiles / ncu, rem = tiles - rounds * ncu;
+  const int64_t m_split = rounds * ncu / tn;
+  return rounds >= 1 && rem * 100 >= 25 * ncu && rem * 100 < 60 * ncu && m_split >= 1 && m_split < tm ? m_split * 256 : 0;
+}
 template <bool AK, bool BK2, int ACT, bool ADD, bool X3 = false, bool PLANES = false, bool F4 = false>
 static void launch_p256(const void* A, const void* B, void* C, const void* bias, const void* addend, void* preact, int64_t M,
                         int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float* colsum, hipStream_t st,
                         const void* A_lo = nullptr, const void* B_lo = nullptr, void* C_lo = nullptr, int nseg = 3, int pre16 = 0) {
   const int tiles_m = (int)((M + 255) / 256), tiles_n = (int)(N / 256);
-  (void)num_cus();
-  if (g_p256_skew < 0) {
-    const char* e = getenv("MMRCA_P256_SKEW");
-    g_p256_skew = e ? atoi(e) : 0;
-  }
-  int grid = tiles_m * tiles_n < g_num_cus ? ((tiles_m * tiles_n) & ~7) : g_num_cus;
+  const int ncu = cu_count();
+  int grid = tiles_m * tiles_n < ncu ? ((tiles_m * tiles_n) & ~7) : ncu;
   if (grid < 8) grid = 8;
   constexpr int LDS_P = 2 * STAGE_BYTES + 32768;       // all 160 KiB of the CU
   // stream-K tail (bf16 and the fused four-plane form; the three-pass bf16x3 form walks its K loop per plane pair)
@@ -894,7 +882,7 @@ static void launch_p256(const void* A, const void* B, void* C, const void* bias,
   MMRCA_MAX_LDS(LDS_P, gemm_p256_k<AK, BK2, ACT, ADD, X3, PLANES, F4>);
   hipLaunchKernelGGL((gemm_p256_k<AK, BK2, ACT, ADD, X3, PLANES, F4>), dim3(grid), dim3(512), LDS_P, st, (const bf16_t*)A, (const bf16_t*)B,
                      (bf16_t*)C, (const bf16_t*)bias, (const bf16_t*)addend, (bf16_t*)preact, M, N, K, lda, ldb, ldc, tiles_m,
-                     tiles_n, colsum, tiles_m * tiles_n >= 2 * g_num_cus ? g_p256_skew : 0, g_mmrca_dbg, (const bf16_t*)A_lo,
+                     tiles_n, colsum, 0, g_mmrca_dbg, (const bf16_t*)A_lo,
                      (const bf16_t*)B_lo, (bf16_t*)C_lo, nseg, pre16, (float*)(sk_ws ? sk_ws + SK_COUNTER_BYTES : nullptr),
                      (unsigned*)sk_ws, sk_split);
 }
@@ -921,19 +909,17 @@ int mmrca_gemm256(const void* A, const void* B, void* C, const void* bias, const
                 "gemm(mfma256): shape / epilogue combination not built");
   MMRCA_REQUIRE(M * lda * 2 < (1ll << 32) && (bk ? K * ldb : N * ldb) * 2 < (1ll << 32) && M * ldc * 2 < (1ll << 32),
                 "gemm(mfma256): operands must be smaller than 4 GiB");
-#define L256(BK_, MODE_, ADD_) launch_p256<false, BK_, MODE_, ADD_>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, colsum, st)
-  if (act == MMRCA_ACT_GELU_SAVE_GRAD) {
-    if (bk) L256(true, MMRCA_ACT_GELU_SAVE_GRAD, false); else L256(false, MMRCA_ACT_GELU_SAVE_GRAD, false);
-  } else if (act == MMRCA_ACT_GELU) {
-    if (bk) L256(true, MMRCA_ACT_GELU, false); else L256(false, MMRCA_ACT_GELU, false);
-  } else if (act == MMRCA_ACT_MUL) {
-    if (bk) L256(true, MMRCA_ACT_MUL, false); else L256(false, MMRCA_ACT_MUL, false);
-  } else if (addend) {
-    if (bk) L256(true, MMRCA_ACT_NONE, true); else L256(false, MMRCA_ACT_NONE, true);
-  } else {
-    if (bk) L256(true, MMRCA_ACT_NONE, false); else L256(false, MMRCA_ACT_NONE, false);
-  }
-#undef L256
+  with_bools([&](auto bk_) {
+    const auto launch = [&](auto mode, auto add) {
+      launch_p256<false, bk_, mode, add>(A, B, C, bias, addend, preact, M, N, K, lda, ldb, ldc, colsum, st);
+    };
+    using std::integral_constant;
+    if (act == MMRCA_ACT_GELU_SAVE_GRAD) launch(integral_constant<int, MMRCA_ACT_GELU_SAVE_GRAD>{}, std::false_type{});
+    else if (act == MMRCA_ACT_GELU) launch(integral_constant<int, MMRCA_ACT_GELU>{}, std::false_type{});
+    else if (act == MMRCA_ACT_MUL) launch(integral_constant<int, MMRCA_ACT_MUL>{}, std::false_type{});
+    else if (addend) launch(integral_constant<int, MMRCA_ACT_NONE>{}, std::true_type{});
+    else launch(integral_constant<int, MMRCA_ACT_NONE>{}, std::false_type{});
+  }, bk);
   MMRCA_CHECK_LAUNCH("gemm(mfma256)");
   return 0;
 }
@@ -945,13 +931,9 @@ bool mmrca_gemm256_x3_ok(int64_t M, int64_t N, int64_t K, int a_layout, int act,
   return act == MMRCA_ACT_NONE || act == MMRCA_ACT_GELU_SAVE_GRAD;
 }
 
-static bool x3_fused_on() {
-  static const int x3_fused = getenv("MMRCA_X3_FUSED") ? atoi(getenv("MMRCA_X3_FUSED")) : 1;
-  return x3_fused != 0;
-}
 // stream-K ranges per leftover tile of a bf16x3 launch (0 = none): only the fused four-plane form walks one K loop per tile
 int mmrca_gemm256_x3_streamk_split(int64_t M, int64_t N, int64_t K, int b_layout, bool has_a_lo, bool has_b_lo, void* stream) {
-  if (!(x3_fused_on() && b_layout != MMRCA_KROW && has_a_lo && has_b_lo && K % 32 == 0 && K >= 64)) return 0;
+  if (!(b_layout != MMRCA_KROW && has_a_lo && has_b_lo && K % 32 == 0 && K >= 64)) return 0;
   return mmrca_gemm256_streamk_split(M, N, K / 32, stream, true);
 }
 
@@ -961,24 +943,21 @@ int mmrca_gemm256_x3(const void* A_hi, const void* A_lo, const void* B_hi, const
   const bool bk = b_layout == MMRCA_KROW;
   MMRCA_REQUIRE(M * lda * 2 < (1ll << 32) && (bk ? K * ldb : N * ldb) * 2 < (1ll << 32) && M * ldc * 4 < (1ll << 32),
                 "gemm_x3(mfma256): operands must be smaller than 4 GiB");
-  // the fused four-plane form (gemm_p256_k<..., F4>): row-major B, all three plane pairs, K % 32 == 0 (MMRCA_X3_FUSED=0: the three-pass form)
-  if (x3_fused_on() && !bk && A_lo && B_lo && K % 32 == 0 && K >= 64) {
-#define L256F(ACT_, PL_) launch_p256<false, false, ACT_, false, true, PL_, true>(A_hi, B_hi, C, bias, nullptr, preact, M, N, K, lda, ldb, ldc, nullptr, st, A_lo, B_lo, C_lo, 3, pre16)
-    if (act == MMRCA_ACT_GELU_SAVE_GRAD) { if (C_lo) L256F(MMRCA_ACT_GELU_SAVE_GRAD, true); else L256F(MMRCA_ACT_GELU_SAVE_GRAD, false); }
-    else { if (C_lo) L256F(MMRCA_ACT_NONE, true); else L256F(MMRCA_ACT_NONE, false); }
-#undef L256F
+  // act is MMRCA_ACT_NONE or MMRCA_ACT_GELU_SAVE_GRAD (mmrca_gemm256_x3_ok); C_lo: the output as two bf16 planes
+  const bool gelu = act == MMRCA_ACT_GELU_SAVE_GRAD, planes = C_lo != nullptr;
+  // the fused four-plane form (gemm_p256_k<..., F4>): row-major B, all three plane pairs, K % 32 == 0
+  if (!bk && A_lo && B_lo && K % 32 == 0 && K >= 64) {
+    with_bools([&](auto gelu_, auto planes_) {
+      launch_p256<false, false, gelu_ ? MMRCA_ACT_GELU_SAVE_GRAD : MMRCA_ACT_NONE, false, true, planes_, true>(
+          A_hi, B_hi, C, bias, nullptr, preact, M, N, K, lda, ldb, ldc, nullptr, st, A_lo, B_lo, C_lo, 3, pre16);
+    }, gelu, planes);
     MMRCA_CHECK_LAUNCH("gemm_x3(mfma256,fused)");
     return 0;
   }
-#define L256X(BK_, ACT_, PL_) launch_p256<false, BK_, ACT_, false, true, PL_>(A_hi, B_hi, C, bias, nullptr, preact, M, N, K, lda, ldb, ldc, nullptr, st, A_lo, B_lo, C_lo, A_lo ? (B_lo ? 3 : 2) : 1, pre16)
-  if (act == MMRCA_ACT_GELU_SAVE_GRAD) {
-    if (C_lo) { if (bk) L256X(true, MMRCA_ACT_GELU_SAVE_GRAD, true); else L256X(false, MMRCA_ACT_GELU_SAVE_GRAD, true); }
-    else { if (bk) L256X(true, MMRCA_ACT_GELU_SAVE_GRAD, false); else L256X(false, MMRCA_ACT_GELU_SAVE_GRAD, false); }
-  } else {
-    if (C_lo) { if (bk) L256X(true, MMRCA_ACT_NONE, true); else L256X(false, MMRCA_ACT_NONE, true); }
-    else { if (bk) L256X(true, MMRCA_ACT_NONE, false); else L256X(false, MMRCA_ACT_NONE, false); }
-  }
-#undef L256X
+  with_bools([&](auto bk_, auto gelu_, auto planes_) {
+    launch_p256<false, bk_, gelu_ ? MMRCA_ACT_GELU_SAVE_GRAD : MMRCA_ACT_NONE, false, true, planes_>(
+        A_hi, B_hi, C, bias, nullptr, preact, M, N, K, lda, ldb, ldc, nullptr, st, A_lo, B_lo, C_lo, A_lo ? (B_lo ? 3 : 2) : 1, pre16);
+  }, bk, gelu, planes);
   MMRCA_CHECK_LAUNCH("gemm_x3(mfma256)");
   return 0;
 }

@@ -12,7 +12,6 @@
 // can be written directly as two planes (C_lo != NULL), which saves that consumer's split pass.
 // Measured logits error of the whole model against a float64 evaluation: 1e-6 (fp32 mode: 5e-7, bf16 mode: 2e-2).
 #include "common.h"
-#include <stdlib.h>
 
 int mmrca_gemm_k1s_x3(const void* A_hi, const void* A_lo, const void* B_hi, const void* B_lo, void* C, void* C_lo, const void* bias,
                       const void* addend, void* preact, float* colsum, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
@@ -23,8 +22,8 @@ int mmrca_gemm256_x3(const void* A_hi, const void* A_lo, const void* B_hi, const
                      hipStream_t st, int pre16);
 
 int mmrca_gemm256_x3_streamk_split(int64_t M, int64_t N, int64_t K, int b_layout, bool has_a_lo, bool has_b_lo, void* stream);
+int64_t mmrca_gemm256_round_split(int64_t M, int64_t N);
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static const int g_x3_tail_pct = getenv("MMRCA_AUTO256_TAIL_PCT") ? atoi(getenv("MMRCA_AUTO256_TAIL_PCT")) : 60;
 
 extern "C" int mmrca_gemm_x3(const void* A_hi, const void* A_lo, const void* B_hi, const void* B_lo, void* C, void* C_lo,
                              const void* bias, const void* addend, void* preact, float* colsum, int64_t M, int64_t N, int64_t K,
@@ -59,18 +58,11 @@ extern "C" int mmrca_gemm_x3(const void* A_hi, const void* A_lo, const void* B_h
     return mmrca_gemm256_x3(A_hi, A_lo, B_hi, B_lo, C, C_lo, bias, preact, M, N, K, lda, ldb, ldc, b_layout, act, st, pre16);
   }
   if (impl == MMRCA_GEMM_AUTO && ok256 && M % 256 == 0 && (M / 256) * (N / 256) >= 256) {
-    // whole rounds of one 256x256 tile per CU on the persistent kernel, a 25-60 % partial round on the 128x128 kernel (gemm.hip AUTO)
-    int ncu = 256, devi = 0;
-    (void)hipGetDevice(&devi);
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, devi) != hipSuccess || ncu < 8) ncu = 256;
-    ncu &= ~7;
-    const int64_t tm = M / 256, tn = N / 256, tiles = tm * tn;
-    const int64_t rounds = tiles / ncu, rem = tiles - rounds * ncu;
-    const int64_t m_split = rounds * ncu / tn;
-    // (a stream-K workspace on this stream keeps the partial round inside the persistent launch: gemm256.hip, round 6)
+    // whole rounds of one 256x256 tile per CU on the persistent kernel, a 25-60 % partial round on the 128x128 kernel
+    // (mmrca_gemm256_round_split; a stream-K workspace on this stream keeps the partial round inside the persistent launch)
     const bool sk_tail = mmrca_gemm256_x3_streamk_split(M, N, K, b_layout, A_lo != nullptr, B_lo != nullptr, stream) >= 2;
-    if (!sk_tail && rounds >= 1 && rem * 100 >= 25 * (int64_t)ncu && rem * 100 < (int64_t)g_x3_tail_pct * ncu && m_split >= 1 && m_split < tm) {
-      const int64_t M1 = m_split * 256;
+    const int64_t M1 = sk_tail ? 0 : mmrca_gemm256_round_split(M, N);
+    if (M1 > 0) {
       if (int rc = mmrca_gemm256_x3(A_hi, A_lo, B_hi, B_lo, C, C_lo, bias, preact, M1, N, K, lda, ldb, ldc, b_layout, act, st, pre16)) return rc;
       const int64_t csz = C_lo ? 2 : 4;
       return mmrca_gemm_k1s_x3((const char*)A_hi + M1 * lda * 2, A_lo ? (const char*)A_lo + M1 * lda * 2 : nullptr, B_hi, B_lo, (char*)C + M1 * ldc * csz,

@@ -28,20 +28,6 @@ from .conv_engine import ConvEncoder, CONV_MODELS
 import os
 
 ALIGN = 64          # arena entries start on 256-byte boundaries
-# Bias gradient as an extra ones-operand MFMA inside the weight-gradient GEMM: parity-tested, measured net-neutral
-# (conditional MFMAs disturb the main loop), off by default.
-FUSE_BIAS_GRAD = os.environ.get("MMRCA_FUSE_BIAS", "0") == "1"
-# The same for the QKV in-projection only (the one linear whose bias gradient no neighbouring kernel produces) on the
-# 128x128x32 weight-gradient kernel, instead of a 232 MB column-sum pass per layer: measured 1.5 % SLOWER end to end
-# (5,720 vs 5,808 samples/s, same box, two rounds) -- the conditional MFMAs cost the main loop more than the pass. Off.
-QKV_BIAS_IN_WGRAD = os.environ.get("MMRCA_QKV_BIAS_IN_WGRAD", "0") == "1"
-# GELU backward fused into the GEMMs: FFN1's forward epilogue stores gelu'(h) instead of h, FFN2's input-gradient
-# epilogue multiplies by it and emits the FFN1 bias gradient (column sums): +3.8 % end to end (no separate pass).
-FUSE_GELU_GRAD = os.environ.get("MMRCA_FUSE_GELU", "1") == "1"
-# weight-gradient GEMMs on a second HIP stream, concurrent with the input-gradient chain of the same layer.  Helped
-# (+4 %) while the GEMMs left the chip half idle; with the current kernels two concurrent GEMMs only fight over LDS
-# slots and L2 (-4 %, same-box A/B), so it is off by default.
-SIDE_STREAM_WGRAD = os.environ.get("MMRCA_SIDE_STREAM", "0") == "1"
 # text encoder and vision encoder are independent until the fusion head: run them on two streams
 CONCURRENT_ENCODERS = os.environ.get("MMRCA_CONCURRENT_ENCODERS", "1") == "1"
 # Only the class-token row of each encoder's LAST layer reaches the head (reference: hidden_state[:, 0] /
@@ -49,15 +35,9 @@ CONCURRENT_ENCODERS = os.environ.get("MMRCA_CONCURRENT_ENCODERS", "1") == "1"
 # FFN, and their backward -- runs on B rows instead of B*S.  Same logits and same gradients for every parameter (the
 # pruned rows' outputs were never read; their gradients are exact zeros); "0" restores the full-row top layer.
 CLS_TAIL = os.environ.get("MMRCA_CLS_TAIL", "1") == "1"
-# weight gradients on the 256x256 split-K kernel (mmrca_gemm_splitk) wherever the shape qualifies; "0" = 128x128 + fp32 atomics
-SPLITK_WGRAD = os.environ.get("MMRCA_SPLITK_WGRAD", "1") == "1"
 # bf16x3 mode: plane pairs per backward product (3 = full; see _lin_bwd_x3).  The forward always runs all three.
 X3_WGRAD_PASSES = int(os.environ.get("MMRCA_X3_WGRAD_PASSES", "3"))
 X3_DGRAD_PASSES = int(os.environ.get("MMRCA_X3_DGRAD_PASSES", "3"))
-# ViT residual adds ride on the NEXT LayerNorm (add_layernorm: s = x + res, y = LN(s)) instead of the GEMM epilogue: the
-# out-projection and FFN2 forward GEMMs become bias-only and qualify for the persistent 256x256 kernel (1,050-1,150 TFLOP/s
-# against 780 for the 128x128 kernel with its addend read); the LayerNorm reads one more operand and writes the sum.
-LN_RESIDUAL = os.environ.get("MMRCA_LN_RESIDUAL", "1") == "1"
 ROWPAD = 256         # (the persistent 256x256 GEMM reads whole 256-row tiles of its A operand)
 
 
@@ -172,8 +152,6 @@ class MMRCAEngine:
         name = dtype.lower() if isinstance(dtype, str) else ""
         self.x3 = name in ("bf16x3", "x3", "bf16x3f", "x3f")
         self.x3f = name in ("bf16x3f", "x3f")
-        if self.x3f and not FUSE_GELU_GRAD:
-            raise L.MmrcaError("bf16x3f needs the fused GELU gradient (MMRCA_FUSE_GELU=1)")
         if self.x3:
             dtype = torch.float32
         elif isinstance(dtype, str):
@@ -219,12 +197,13 @@ class MMRCAEngine:
         self.head_span = self.arena.span(self.head_keys[0][0], self.head_keys[-1][0])
         self._bufs: Dict[Tuple, torch.Tensor] = {}
         # bf16x3: gelu(h) and its gradient only feed other bf16x3 GEMMs, so their epilogues write them as two bf16 planes
-        self._g_planes = self.x3 and FUSE_GELU_GRAD and os.environ.get("MMRCA_X3_PLANES_OUT", "1") == "1"
+        self._g_planes = self.x3
         self._plane_valid = set()
         self._plane_fresh = set()
         self._ln_planes = self._g_planes
-        # FFN1's epilogue: gelu + gelu' (bf16x3f: gelu' as bf16, what its bf16 backward multiplies by)
-        self._gelu_act = (L.ACT_GELU_SAVE_GRAD_BF16 if self.x3f else L.ACT_GELU_SAVE_GRAD) if FUSE_GELU_GRAD else L.ACT_GELU
+        # FFN1's epilogue: gelu + gelu' (bf16x3f: gelu' as bf16, what its bf16 backward multiplies by).  The GELU backward is fused
+        # into the GEMMs: FFN2's input-gradient epilogue multiplies by gelu' and emits the FFN1 bias gradient (column sums): +3.8 %.
+        self._gelu_act = L.ACT_GELU_SAVE_GRAD_BF16 if self.x3f else L.ACT_GELU_SAVE_GRAD
         self._hdt = torch.bfloat16 if self.x3f else None
         self._saved = None
         # parameter groups that become final together during backward; they tile the arena exactly (padding included)
@@ -239,11 +218,10 @@ class MMRCAEngine:
             self.groups[gname] = (lo, hi)
         self.grad_sync = None          # distributed.GradSync, set by the training driver
         on_gpu = self.device.type == "cuda"
-        self._side_v = torch.cuda.Stream(device=self.device) if (SIDE_STREAM_WGRAD and on_gpu) else None
-        self._side_t = torch.cuda.Stream(device=self.device) if (SIDE_STREAM_WGRAD and on_gpu) else None
-        self._side = self._side_v          # the side stream of the encoder whose backward is being queued
+        # (weight gradients run on the stream of their encoder's backward: a second stream for them measured -4 %.  bench.py's
+        # single-stream replay still saves and clears these three attributes.)
+        self._side_v = self._side_t = self._side = None
         self._text_stream = torch.cuda.Stream(device=self.device) if (CONCURRENT_ENCODERS and on_gpu) else None
-        self._first_wgrad_ev = None
         self._head_w = self._head_struct("p")
         self._head_g = self._head_struct("g")
         # fused QKV views of the text encoder must be contiguous in the arena
@@ -475,10 +453,10 @@ class MMRCAEngine:
         L.gemm(x, w, out, bias=b, addend=addend, preact=preact, M=M, N=N, K=K, lda=K, ldb=K, ldc=N,
                a_layout=L.ROWK, b_layout=L.ROWK, act=act, dtype=self.dt, impl=self.gemm_impl)
 
-    def _lin_bwd(self, dy, x, wkey, bkey, dx, M, N, K, addend=None, wnumel=None, gelu_h=None, bias_done=False, gelu_db=None,
-                 fuse_db=False):
-        """dy [M,N], x [M,K], weight [N,K]:  dW += dy^T x and db += colsum(dy) in ONE pass (the bias gradient rides
-        on the weight-gradient GEMM); dx = dy W (+ addend), optionally times gelu'(gelu_h) in the epilogue."""
+    def _lin_bwd(self, dy, x, wkey, bkey, dx, M, N, K, addend=None, wnumel=None, gelu_h=None, bias_done=False, gelu_db=None):
+        """dy [M,N], x [M,K], weight [N,K]:  dW += dy^T x and db += colsum(dy) (bias_done: the producer of dy already accumulated
+        its column sums); dx = dy W (+ addend), times gelu'(gelu_h) in the epilogue, which then also emits the column sums of dx
+        into gelu_db (the FFN1 bias gradient)."""
         Mk = _round_up(M, 64)
         gw = self.G(wkey) if wnumel is None else self.Gflat(wkey, wnumel)
         gb = self.G(bkey) if wnumel is None else self.Gflat(bkey, N)
@@ -487,43 +465,21 @@ class MMRCAEngine:
         if self.x3f:
             x = self._hi(x, M, K)
         bdt = self.bdt
-
-        def wgrad():
-            fused = (FUSE_BIAS_GRAD or fuse_db) and not bias_done
-            if SPLITK_WGRAD and not fused and self.gemm_impl == L.IMPL_AUTO and L.gemm_splitk_ok(N, K, Mk, bdt):
-                # 256x256 tiles, partial tiles through a per-stream workspace, no atomics (1,020-1,150 vs 800-870 TFLOP/s)
-                L.gemm_splitk(dy, x, gw, self._splitk_ws(), M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K)
-            else:
-                L.gemm(dy, x, gw, bias=(gb if fused else None), M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K, a_layout=L.KROW,
-                       b_layout=L.KROW, accum=True, dtype=bdt, impl=self.gemm_impl)
-            if not fused and not bias_done:     # bias_done: the producer of dy already accumulated its column sums
-                L.colsum_accum(dy, gb, M, N, N, bdt)
-
-        if self._side is None:
-            wgrad()
+        if self.gemm_impl == L.IMPL_AUTO and L.gemm_splitk_ok(N, K, Mk, bdt):
+            # 256x256 tiles, partial tiles through a per-stream workspace, no atomics (1,020-1,150 vs 800-870 TFLOP/s)
+            L.gemm_splitk(dy, x, gw, self._splitk_ws(), M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K)
         else:
-            # dy and x are complete on the main stream here; the side stream reads them while the main stream goes on
-            # with the input-gradient chain.  Buffers are only re-written in the next layer (after _layer_boundary) or,
-            # for the incoming-gradient buffer, after _wait_first_wgrad().
-            main = torch.cuda.current_stream()
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                wgrad()
-                if self._first_wgrad_ev is None:
-                    self._first_wgrad_ev = torch.cuda.Event()
-                    self._first_wgrad_ev.record(self._side)
+            L.gemm(dy, x, gw, M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K, a_layout=L.KROW, b_layout=L.KROW, accum=True, dtype=bdt,
+                   impl=self.gemm_impl)
+        if not bias_done:
+            L.colsum_accum(dy, gb, M, N, N, bdt)
         if dx is not None:
             w = self.Wb(wkey, wnumel)
-            fuse = gelu_h is not None and FUSE_GELU_GRAD
+            fuse = gelu_h is not None
             # fused: dh = (dy W) * gelu'(h) in the epilogue (h holds gelu' then) and the FFN1 bias gradient = its column sums
             L.gemm(dy, w, dx, addend=addend, preact=(gelu_h if fuse else None), M=M, N=K, K=N, lda=N, ldb=K, ldc=K,
                    a_layout=L.ROWK, b_layout=L.KROW, act=(L.ACT_MUL if fuse else L.ACT_NONE), dtype=bdt,
                    impl=self.gemm_impl, colsum=(gelu_db if fuse else None))
-            if gelu_h is not None and not fuse:
-                if gelu_db is not None:     # dh = dg * gelu'(h) and the FFN1 bias gradient (column sums of dh) in one pass
-                    L.gelu_bwd_colsum(dx, gelu_h, dx, gelu_db, M, K, K, bdt)
-                else:
-                    L.gelu_bwd(dx, gelu_h, dx, M * K, bdt)
 
     def _lin_bwd_x3(self, dy, x, wkey, dx, M, N, K, Mk, gw, gb, addend, wnumel, gelu_h, bias_done, gelu_db):
         """bf16x3 form of _lin_bwd: dy is split once for both products, x's planes are the ones its forward GEMM made"""
@@ -532,43 +488,23 @@ class MMRCAEngine:
         # pass sets of the backward products (csrc/gemm_x3.hip): 3 = hi.hi + lo.hi + hi.lo; 2 drops the lo plane of the non-gradient
         # operand (x for the weight gradient, W for the input gradient: that operand enters at bf16 precision); 1 = hi.hi only
         wg_a, wg_b = (dyp, xp) if X3_WGRAD_PASSES >= 3 else ((dyp, (xp[0], None)) if X3_WGRAD_PASSES == 2 else ((dyp[0], None), (xp[0], None)))
-
-        def wgrad():
-            if SPLITK_WGRAD and self.gemm_impl == L.IMPL_AUTO and L.gemm_splitk_ok(N, K, Mk, L.BF16):
-                L.gemm_splitk_x3(wg_a, wg_b, gw, self._splitk_ws(), M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K)
-            else:
-                L.gemm_x3(wg_a, wg_b, gw, M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K, a_layout=L.KROW, b_layout=L.KROW, accum=True)
-            if not bias_done:
-                if isinstance(dy, Planes):
-                    raise L.MmrcaError("bf16x3: the bias gradient of a two-plane dY must come from its producer (bias_done)")
-                L.colsum_accum(dy, gb, M, N, N, self.dt)
-
-        if self._side is None:
-            wgrad()
+        if self.gemm_impl == L.IMPL_AUTO and L.gemm_splitk_ok(N, K, Mk, L.BF16):
+            L.gemm_splitk_x3(wg_a, wg_b, gw, self._splitk_ws(), M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K)
         else:
-            main = torch.cuda.current_stream()
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                wgrad()
-                if self._first_wgrad_ev is None:
-                    self._first_wgrad_ev = torch.cuda.Event()
-                    self._first_wgrad_ev.record(self._side)
+            L.gemm_x3(wg_a, wg_b, gw, M=N, N=K, K=Mk, lda=N, ldb=K, ldc=K, a_layout=L.KROW, b_layout=L.KROW, accum=True)
+        if not bias_done:
+            if isinstance(dy, Planes):
+                raise L.MmrcaError("bf16x3: the bias gradient of a two-plane dY must come from its producer (bias_done)")
+            L.colsum_accum(dy, gb, M, N, N, self.dt)
         if dx is not None:
-            fuse = gelu_h is not None and FUSE_GELU_GRAD
+            fuse = gelu_h is not None
             po = isinstance(dx, Planes)
-            if po and gelu_h is not None and not fuse:
-                raise L.MmrcaError("bf16x3 mode with a two-plane FFN gradient needs the fused GELU gradient (MMRCA_FUSE_GELU=1)")
             wp = self.Wx3(wkey, wnumel)
             dg_a, dg_b = (dyp, wp) if X3_DGRAD_PASSES >= 3 else ((dyp, (wp[0], None)) if X3_DGRAD_PASSES == 2 else ((dyp[0], None), (wp[0], None)))
             L.gemm_x3(dg_a, dg_b, dx.hi if po else dx, C_lo=(dx.lo if po else None), addend=addend,
                       preact=(gelu_h if fuse else None), colsum=(gelu_db if fuse else None),
                       M=M, N=K, K=N, lda=N, ldb=K, ldc=K, a_layout=L.ROWK, b_layout=L.KROW, act=(L.ACT_MUL if fuse else L.ACT_NONE),
                       impl=self.gemm_impl)
-            if gelu_h is not None and not fuse:
-                if gelu_db is not None:
-                    L.gelu_bwd_colsum(dx, gelu_h, dx, gelu_db, M, K, K, self.dt)
-                else:
-                    L.gelu_bwd(dx, gelu_h, dx, M * K, self.dt)
 
     def _ln_fwd(self, x, res, pfx, sum_out, y, mean, rstd, rows, D, eps, ld_x=None, ld_y=None, in_drop=(0.0, 0), out_drop=(0.0, 0),
                 to_gemm=False):
@@ -629,19 +565,6 @@ class MMRCAEngine:
             self._plane_fresh.add(key)
             return
         L.mha_fwd(qkv, mask32, ctx, lse, B, H, S, dh, dh ** -0.5, self.dt, self.attn_impl, drop_p=drop_p, drop_seed=drop_seed, cu=cu)
-
-    def _layer_boundary(self):
-        """All side-stream weight-gradient work of the finished layer must be done before the next layer re-writes the
-        gradient buffers it read (and before its parameter group is handed to the gradient all-reduce)."""
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
-            self._first_wgrad_ev = None
-
-    def _wait_first_wgrad(self):
-        """The first weight-gradient GEMM of a layer reads the incoming-gradient buffer that the layer's last op
-        overwrites with the outgoing gradient."""
-        if self._side is not None and self._first_wgrad_ev is not None:
-            torch.cuda.current_stream().wait_event(self._first_wgrad_ev)
 
     @staticmethod
     def _site_seed(base: int, layer: int, site: int) -> int:
@@ -772,10 +695,7 @@ class MMRCAEngine:
             qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "tg", B * T, B)
             L.mha_bwd(qkv_b, sv["mask32"], ctx_b, dctx, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt, self.attn_impl,
                       drop_p=dp, drop_seed=sd(i, 1), cu=cu)
-            self._wait_first_wgrad()       # (the FFN2 weight gradient does not read dx in the post-LN layout; harmless)
-            self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1, wnumel=3 * D * D,
-                          fuse_db=QKV_BIAS_IN_WGRAD)
-            self._layer_boundary()
+            self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1, wnumel=3 * D * D)
             self._ready(f"text_layer_{i}")
         ds0 = gb("ds2", D)
         self._ln_bwd(dx, sv["emb"], P + "embeddings.LayerNorm", sv["mean0"], sv["rstd0"], None, ds0, M, D,
@@ -784,7 +704,6 @@ class MMRCAEngine:
         L.embed_bwd(ds0, sv["ids32"], sv["pos"], self.G(P + "embeddings.word_embeddings.weight"),
                     self.G(P + "embeddings.position_embeddings.weight"), dtype_row, M, D, self.bdt,
                     pad_id=s.pad_id, pos_pad_id=(s.pad_id if s.pos_offset else -1))
-        self._layer_boundary()
         self._ready("text_emb", flush=True)
 
     def _text_backward_tail(self, dcls, sv, dx):
@@ -825,9 +744,7 @@ class MMRCAEngine:
         qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "tg", B * T, B)
         L.mha_cls_bwd(qkv_b, sv["mask32"], ctx_b, dctx_c, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt,
                       drop_p=dp, drop_seed=sd(i, 1), cu=cu)
-        self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1_full, wnumel=3 * D * D,
-                      fuse_db=QKV_BIAS_IN_WGRAD)
-        self._layer_boundary()
+        self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1_full, wnumel=3 * D * D)
         self._ready(f"text_layer_{i}")
 
     # ------------------------------------------------------------------ vision encoder
@@ -848,7 +765,10 @@ class MMRCAEngine:
         x = fb("x", M, D, 0)
         L.vit_assemble_fwd(proj, self.W(P + "class_token"), self.W(P + "encoder.pos_embedding"), x, B, nP, D, self.dt)
         layers = []
-        fuse_res = LN_RESIDUAL and (self.dt == L.BF16 or self.x3)
+        # ViT residual adds ride on the NEXT LayerNorm (add_layernorm: s = x + res, y = LN(s)) instead of the GEMM epilogue: the
+        # out-projection and FFN2 forward GEMMs become bias-only and qualify for the persistent 256x256 kernel (1,050-1,150 TFLOP/s
+        # against 780 for the 128x128 kernel with its addend read); the LayerNorm reads one more operand and writes the sum.
+        fuse_res = self.dt == L.BF16 or self.x3
         pend = None                      # (ffn2 output, x1) of the previous layer whose sum -- this layer's input -- is still to be formed
         for i in range(s.layers):
             Lk = P + f"encoder.layers.encoder_layer_{i}."
@@ -955,17 +875,13 @@ class MMRCAEngine:
             qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "vg", M, B)
             L.mha_bwd(qkv_b, None, ctx_b, dctx, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt, self.attn_impl)
             dy1 = gb("dy", M, D)
-            self._lin_bwd(dqkv, a["y1"], Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", dy1, M, 3 * D, D,
-                          fuse_db=QKV_BIAS_IN_WGRAD)
-            self._wait_first_wgrad()       # mlp.3's weight gradient (side stream) reads dx; this op overwrites it
+            self._lin_bwd(dqkv, a["y1"], Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", dy1, M, 3 * D, D)
             below = P + f"encoder.layers.encoder_layer_{i - 1}.mlp.3.bias"
             self._ln_bwd(dy1, a["x"], Lk + "ln_1", a["m1"], a["r1"], dx1, dx, M, D, dcol=(self.G(below) if i > 0 else None))
-            self._layer_boundary()
             self._ready(f"image_layer_{i}")
         dproj = gb("dproj", B * nP, D)
         L.vit_assemble_bwd(dx, dproj, self.Gflat(P + "class_token", D), self.Gflat(P + "encoder.pos_embedding", Tn * D), B, nP, D, self.bdt)
         self._lin_bwd(dproj, sv["patches"], P + "conv_proj.weight", P + "conv_proj.bias", None, B * nP, D, Kp, wnumel=D * Kp)
-        self._layer_boundary()
         self._ready("image_emb", flush=True)
 
     def _vision_backward_tail(self, dxc, sv, dx):
@@ -997,11 +913,9 @@ class MMRCAEngine:
         qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "vg", M, B)
         L.mha_cls_bwd(qkv_b, None, ctx_b, dctx_c, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt)
         dy1 = gb("dy", M, D)
-        self._lin_bwd(dqkv, a["y1"], Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", dy1, M, 3 * D, D,
-                      fuse_db=QKV_BIAS_IN_WGRAD)
+        self._lin_bwd(dqkv, a["y1"], Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", dy1, M, 3 * D, D)
         below = P + f"encoder.layers.encoder_layer_{i - 1}.mlp.3.bias"
         self._ln_bwd(dy1, a["x"], Lk + "ln_1", a["m1"], a["r1"], dx1, dx, M, D, dcol=(self.G(below) if i > 0 else None))
-        self._layer_boundary()
         self._ready(f"image_layer_{i}")
 
     # ------------------------------------------------------------------ whole model
@@ -1069,20 +983,15 @@ class MMRCAEngine:
             self._text_stream.wait_stream(main)
             dtxt.record_stream(self._text_stream)
             if train_image:
-                self._side = self._side_v
                 self._image_backward(dimg, sv["vision"])
             with torch.cuda.stream(self._text_stream):
-                self._side = self._side_t
                 self._text_backward(dtxt, sv["text"])
             main.wait_stream(self._text_stream)
         else:
             if train_image:
-                self._side = self._side_v
                 self._image_backward(dimg, sv["vision"])
             if train_text:
-                self._side = self._side_t
                 self._text_backward(dtxt, sv["text"])
-        self._side = self._side_v
         self.arena.lp_valid = False        # an optimizer step normally follows
 
     # ------------------------------------------------------------------ flat-arena optimizer steps

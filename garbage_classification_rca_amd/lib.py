@@ -160,8 +160,6 @@ def load(build_if_missing: bool = False):
     lib.mmrca_last_error.restype = C.c_char_p
     lib.mmrca_version.restype = C.c_int
     _lib = lib
-    if os.environ.get("MMRCA_DBG"):            # kernel ablation / probe bits (csrc: g_mmrca_dbg); never set in production runs
-        lib.mmrca_debug_set(int(os.environ["MMRCA_DBG"]))
     return lib
 
 
@@ -234,8 +232,7 @@ CONV_PROFILE = None     # bench.py sets this to a list: (kernel family, algorith
 
 
 _STREAMK_WS = {}       # (device index, stream) -> zero-filled workspace registered with mmrca_gemm_streamk_workspace
-STREAMK = os.environ.get("MMRCA_SK", "1") != "0"     # the library applies it to the fused bf16x3 products only ...
-STREAMK_BF16 = os.environ.get("MMRCA_SK_BF16", "0") == "1"   # ... unless this asks for the plain bf16 products too (measured neutral)
+STREAMK = os.environ.get("MMRCA_SK", "1") != "0"     # the library applies it to the fused bf16x3 products (mmrca_gemm_streamk_config)
 
 
 def streamk_workspace(M, N, device, force=False):
@@ -266,8 +263,6 @@ def gemm(A, B, Cout, *, bias=None, addend=None, preact=None, M, N, K, lda, ldb, 
     rows_readable = (rows of A, rows of the side operand) that exist in memory: required for impl=IMPL_MFMA256 with a ragged M
     (mmrca_gemm_rows; the 256x256 kernel reads whole 256-row tiles)"""
     _dev(A, "gemm A")
-    if STREAMK_BF16 and dtype == BF16 and not accum:
-        streamk_workspace(M, N, A.device)
     if rows_readable is not None:
         if accum:
             raise MmrcaError("gemm: rows_readable is not available in accumulate mode")

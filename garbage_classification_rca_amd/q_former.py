@@ -343,7 +343,7 @@ class Blip2QFormerEngine:
         # GEMMs run over whole 256-row tiles of the (zero-padded) buffers: that is what lets the dispatcher give the
         # persistent 256x256 kernel the shapes it takes (N % 256 == 0: FFN1 and the Q-Former's K|V projection); rows >= M
         # are never read by the attention or the LayerNorms.  The residual adds ride on the GEMM epilogues (addend): moving
-        # them onto the next LayerNorm, as engine.LN_RESIDUAL does for ViT-B, measured slower here (N = 1408 cannot use the
+        # them onto the next LayerNorm, as the ViT-B encoder in engine.py does, measured slower here (N = 1408 cannot use the
         # 256-wide kernel that move pays for; the LayerNorm got 20 us slower per call, the GEMMs 3 us faster).
         Mg = _round_up(M, ROWPAD) if self.dtype == torch.bfloat16 else M
         if Mg > M:

@@ -633,9 +633,8 @@ def test_gemm_streamk_tail_under_the_fused_bf16x3_form(K, act, streamk, monkeypa
     assert not torch.equal(a, b), "the two walks add in a different order: identical outputs would mean the tail did not run"
 
 
-def test_gemm_streamk_tail_on_a_side_stream_and_through_auto(streamk, monkeypatch):
+def test_gemm_streamk_tail_on_a_side_stream_and_through_auto_with_workspaces_registered_per_stream(streamk, monkeypatch):
     monkeypatch.setattr(L, "STREAMK", True)
-    monkeypatch.setattr(L, "STREAMK_BF16", True)
     """one workspace per stream (two streams run GEMMs concurrently in the engine); AUTO keeps the partial round inside the launch
     instead of handing it to the 128x128 kernel"""
     M, N, K = 50432, 768, 768
@@ -647,12 +646,46 @@ def test_gemm_streamk_tail_on_a_side_stream_and_through_auto(streamk, monkeypatc
     side = torch.cuda.Stream()
     for st in (torch.cuda.current_stream(), side):
         with torch.cuda.stream(st):
+            L.streamk_workspace(M, N, X.device, force=True)
             Y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
             L.gemm(X, W, Y, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, dtype=L.BF16)
             outs.append(Y)
     torch.cuda.synchronize()
     assert len(L._STREAMK_WS) >= 2
     assert rel_err(outs[0], ref) < 1e-2 and torch.equal(outs[0], outs[1])
+
+
+def test_gemm_streamk_registry_full_leaves_the_extra_stream_without_a_tail(streamk):
+    """the library keeps at most 32 (device, stream) workspaces: registering one more is not an error, that stream simply runs
+    without the stream-K tail (whole rounds + the 128x128 kernel) and its products are the tail-less ones"""
+    M, N, K = 50432, 768, 768
+    lib = L.load()
+    g = torch.Generator().manual_seed(5)
+    X = dev(torch.randn(M, K, generator=g) * 0.5, torch.bfloat16)
+    W = dev(torch.randn(N, K, generator=g) * 0.05, torch.bfloat16)
+    ref = X.double() @ W.double().t()
+    ws = L._STREAMK_WS[(torch.cuda.current_device(), L.stream_ptr())]
+    fake = list(range(1, 33))          # registry keys only: no launch is ever made on these handles
+    side = torch.cuda.Stream()
+    try:
+        for key in fake:               # 32 more entries fill the registry whatever was registered before
+            L._check(lib.mmrca_gemm_streamk_workspace(L.ptr(ws), ws.numel(), key), "streamk register")
+        with torch.cuda.stream(side):
+            L.streamk_workspace(M, N, X.device, force=True)        # used to raise MmrcaError
+            Y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            L.gemm(X, W, Y, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, dtype=L.BF16)
+        torch.cuda.current_stream().wait_stream(side)
+        _streamk_toggle(False)         # the current stream without its workspace: the tail-less split
+        try:
+            Z = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            L.gemm(X, W, Z, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, dtype=L.BF16)
+        finally:
+            _streamk_toggle(True)
+        torch.cuda.synchronize()
+    finally:
+        for key in fake:
+            L._check(lib.mmrca_gemm_streamk_workspace(None, ws.numel(), key), "streamk unregister")
+    assert rel_err(Y, ref) < 1e-2 and torch.equal(Y, Z)
 
 
 def test_gemm_at_the_benchmarked_sizes():
