@@ -130,6 +130,8 @@ _SIGS = {
     "mmrca_adamw_step": [_vp] * 5 + [_i64] + [_f32] * 5 + [_i32, _f32, _vp],
     "mmrca_cast_f32_to_bf16": [_vp, _vp, _i64, _vp],
     "mmrca_seed_epoch_set": [_vp, _u64, _vp],
+    "mmrca_linear_cls_fwd": [_vp, _i32, _vp, _vp, _vp] + [_i32] * 3 + [_f32, _u64, _i32, _vp],
+    "mmrca_linear_cls_bwd": [_vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 3 + [_f32, _u64, _i32, _vp],
     "mmrca_sd_rowscale": [_vp, _vp, _i32, _i32, _u64, _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["mmrca_last_error", "mmrca_version", "mmrca_debug_set", "mmrca_bn_flat_set", "mmrca_debug_attn_stamps", "mmrca_gemm_splitk_workspace_bytes", "mmrca_gemm_streamk_workspace_bytes",
@@ -546,6 +548,22 @@ def head_bwd(dlogits, img, txt, w: HeadPtrs, g: HeadPtrs, dimg, dtxt, B, d_img, 
         _check(load().mmrca_head_bwd(ptr(dlogits), ptr(img), ptr(txt), C.byref(w), C.byref(g), ptr(dimg), ptr(dtxt), B, d_img, d_txt,
                                      n_classes, int(reverse), mode, drop_p, seed, dtype, ptr(workspace),
                                      workspace.numel() * workspace.element_size(), stream_ptr()), "mmrca_head_bwd")
+
+
+def linear_cls_fwd(feat, ld, W, b, logits, B, F, Cc, drop_p, seed, dtype):
+    """logits [B,C] fp32 = (feat * keep / (1 - drop_p)) W^T + b; feat rows of stride ``ld`` (elements) in ``dtype``"""
+    _dev(feat, "linear_cls feat")
+    with _Bracket("linear_cls_fwd", (B, F, Cc)):
+        _check(load().mmrca_linear_cls_fwd(ptr(feat), ld, ptr(W), ptr(b), ptr(logits), B, F, Cc, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           dtype, stream_ptr()), "mmrca_linear_cls_fwd")
+
+
+def linear_cls_bwd(dlogits, feat, ld, W, dW, db, dfeat, B, F, Cc, drop_p, seed, dtype):
+    """dW / db are ACCUMULATED (fixed-order reduction over B, no atomics); dfeat (optional) [B, F] in ``dtype`` with the forward's mask"""
+    _dev(dlogits, "linear_cls dlogits")
+    with _Bracket("linear_cls_bwd", (B, F, Cc)):
+        _check(load().mmrca_linear_cls_bwd(ptr(dlogits), ptr(feat), ld, ptr(W), ptr(dW), ptr(db), ptr(dfeat), B, F, Cc, float(drop_p),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, dtype, stream_ptr()), "mmrca_linear_cls_bwd")
 
 
 def xent_fwd_bwd(logits, labels, class_w, smoothing, loss, dlogits, B, Cc, grad_scale=1.0):

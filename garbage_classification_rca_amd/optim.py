@@ -23,9 +23,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return self.engine.trainable_spans(tt, ti)
 
     def _named_spans(self):
-        """(name, lo, hi) of the trainable arena spans, never merged: text encoder | image encoder | head."""
+        """(name, lo, hi) of the trainable arena spans, never merged: text encoder | image encoder | head (either encoder may be absent)."""
         tt, ti = self.model._train_flags()
-        i0, h0 = self.engine.groups["image_emb"][0], self.engine.groups["head"][0]
+        h0 = self.engine.groups["head"][0]
+        i0 = self.engine.groups["image_emb"][0] if "image_emb" in self.engine.groups else h0    # (a text-only classifier has no image span)
         out = []
         if tt:
             out.append(("text", 0, i0))

@@ -477,6 +477,18 @@ int mmrca_head_bwd(const float* dlogits, const void* img, const void* txt, const
                    int reverse, int mode, float drop_p, uint64_t seed, int dtype, void* workspace,
                    int64_t workspace_bytes, void* stream);
 
+/* K1b. linear classification head of the single-backbone classifiers (classifiers.py; torchvision's heads.head / classifier /
+ * fc and the text models' drop + out, CVPR_code/text_models.py):  logits[B,C] (fp32) = (feat * keep / (1 - drop_p)) W^T + b.
+ * feat: [B, F] rows with row stride `ld` (elements) in `dtype` (bf16 | fp32); W [C, F], b [C]: fp32.  Every product in fp32.
+ * keep(b, f) = the counter hash of (seed + mask epoch, b*F + f) >= drop_p  (mmrca_seed_epoch_set applies).
+ * F and ld multiples of 4, feat aligned to 4 elements, C <= 16.  One launch each.
+ * bwd: dW [C,F] += sum_b dlogits[b,:]^T xd[b,:], db [C] += sum_b dlogits[b,:], reduced over B in a fixed order without atomics
+ * (bitwise reproducible) and ACCUMULATED like mmrca_head_bwd; dfeat (optional) [B, F] contiguous, in `dtype`, the same mask applied. */
+int mmrca_linear_cls_fwd(const void* feat, int ld, const float* W, const float* b, float* logits, int B, int F, int C,
+                         float drop_p, uint64_t seed, int dtype, void* stream);
+int mmrca_linear_cls_bwd(const float* dlogits, const void* feat, int ld, const float* W, float* dW, float* db, void* dfeat,
+                         int B, int F, int C, float drop_p, uint64_t seed, int dtype, void* stream);
+
 /* K6. weighted, label-smoothed cross entropy (torch.nn.CrossEntropyLoss as built at main_both.py:87-93), mean
  * reduction with the weighted denominator.  loss: fp32[1]; dlogits (optional): fp32 [B,C] scaled by grad_scale. */
 int mmrca_xent_fwd_bwd(const float* logits, const int32_t* labels, const float* class_w, float smoothing,
