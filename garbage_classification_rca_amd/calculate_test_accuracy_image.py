@@ -18,7 +18,7 @@ from .classifiers import IMAGE_FACTORIES
 from .options import args_parser
 from .single_modality import calculate_test_accuracy, invalid_model, write_report
 
-BATCHES = {"transformer_B16": 128, "transformer_L16": 128, "eff_v2_medium": 32, "eff_v2_large": 8, "shuffle_net": 128}
+BATCHES = {"transformer_B16": 128, "transformer_L16": 128, "eff_v2_medium": 32, "eff_v2_large": 8, "shuffle_net": 128, "mb": 256}
 
 
 def main(argv=None):

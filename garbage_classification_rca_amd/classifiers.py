@@ -9,17 +9,19 @@ autograd node (``loss.backward()`` runs the HIP backward and accumulates into ``
 * ViT: torchvision's ``vit_b_16`` / ``vit_l_16`` keys, head ``heads.head.*``;
 * EfficientNetV2: ``features.0`` .. ``features.8`` (BatchNorm buffers included), head ``classifier.1.*``;
 * ShuffleNetV2: ``conv1``, ``stage2`` .. ``stage4``, ``conv5``, head ``fc.*``;
+* MobileNetV3-Large: ``features.0`` .. ``features.16`` and ``classifier.0`` (BatchNorm buffers included), head ``classifier.3.*``;
 * text: ``model.<transformers keys>`` (RoBERTa's unused ``model.pooler`` included, as ``RobertaModel`` builds it), head ``out.*``.
 
 What the head sees (models.py / text_models.py): ViT the ``encoder.ln`` output of the class token, no dropout (torchvision's ``heads`` is
 a Linear alone); EfficientNetV2 the average-pooled ``features.8`` output behind ``classifier[0] = Dropout(0.3 / 0.4)``; ShuffleNetV2 the
-mean-pooled ``conv5`` output, no dropout; text models ``last_hidden_state[:, 0]`` behind ``Dropout(drop_ratio)``, with the encoders'
+mean-pooled ``conv5`` output, no dropout; MobileNetV3-Large the hard-swish of ``classifier.0`` (Linear 960 -> 1280 on the pooled
+``features.16`` output) behind ``Dropout(0.2)``; text models ``last_hidden_state[:, 0]`` behind ``Dropout(drop_ratio)``, with the encoders'
 own dropout of 0.1 in train mode.
 
 Freezing follows the reference: an image model with ``transfer_learning=True`` freezes its backbone (the head stays trainable), a text
 model always freezes its encoder in the constructor.  No pretrained weights can be fetched here: parameters are initialised as
 ``MM_RCA`` initialises them (engine.init_parameters).  Additive keyword arguments: ``dtype`` (the ``MM_RCA`` modes, default
-``"bf16x3f"``), ``device``, ``init_seed``, and ``image_size`` for the conv backbones.
+``"bf16x3f"``), ``device``, ``init_seed``, and ``image_size`` for the conv backbones (default 480 EfficientNetV2, 320 MobileNetV3, 224 else).
 """
 from __future__ import annotations
 
@@ -33,9 +35,11 @@ from .classifier_engine import ClassifierEngine
 from .multimodal_model import HashingTokenizer, ParamTree, _EngineFunction
 
 # dropout in front of the Linear (torchvision efficientnet_v2_m / _l: classifier = Sequential(Dropout(p), Linear))
-IMAGE_HEAD_DROPOUT = {"transformer_B16": 0.0, "transformer_L16": 0.0, "eff_v2_medium": 0.3, "eff_v2_large": 0.4, "shuffle_net": 0.0}
+# (mobilenet_v3_large: classifier = Sequential(Linear(960, 1280), Hardswish, Dropout(0.2), Linear) -- the first two are the backbone's)
+IMAGE_HEAD_DROPOUT = {"transformer_B16": 0.0, "transformer_L16": 0.0, "eff_v2_medium": 0.3, "eff_v2_large": 0.4, "shuffle_net": 0.0, "mb": 0.2}
 HEAD_NAME = {"transformer_B16": "heads.head", "transformer_L16": "heads.head", "eff_v2_medium": "classifier.1",
-             "eff_v2_large": "classifier.1", "shuffle_net": "fc", "distilbert": "out", "bert": "out", "roberta": "out"}
+             "eff_v2_large": "classifier.1", "shuffle_net": "fc", "mb": "classifier.3", "distilbert": "out", "bert": "out", "roberta": "out"}
+DEFAULT_IMAGE_SIZE = {"eff_v2_medium": 480, "eff_v2_large": 480, "mb": 320}      # (main_image.py: the reference's input sizes; others 224)
 # the EfficientNetV2 extractor's attribute names (conv_engine.py, the MM_RCA checkpoint names) -> torchvision's `features` index
 _EFF_FEATURES = {"stem.0": "features.0", "stem.1": "features.1", "stage1": "features.2", "stage2": "features.3", "stage3": "features.4",
                  "stage4": "features.5", "stage5": "features.6", "stage6": "features.7", "final_conv": "features.8"}
@@ -71,7 +75,7 @@ class SingleBackboneClassifier(torch.nn.Module):
         if backbone in S.VISION_SPECS:
             self.image_size = S.VISION_SPECS[backbone].image
         else:
-            self.image_size = int(image_size or (480 if backbone in ("eff_v2_medium", "eff_v2_large") else 224))
+            self.image_size = int(image_size or DEFAULT_IMAGE_SIZE.get(backbone, 224))
         self.engine = ClassifierEngine(backbone, n_classes, dtype, device, image_size=self.image_size)
         self.engine.init_parameters(init_seed)
         self.kind, self.n_classes = self.engine.kind, n_classes
@@ -223,6 +227,12 @@ def ShuffleNetV2(num_classes=4, transfer_learning=False, **kw):
     return _image("shuffle_net", num_classes, transfer_learning, kw)
 
 
+def MBNetLarge(num_classes=4, transfer_learning=False, **kw):
+    """models.py MBNetLarge: torchvision mobilenet_v3_large, classifier[3] = Linear(1280, num_classes) behind Dropout(0.2); the
+    transfer-learning freeze covers features.* and classifier.0 (the backbone), the head classifier.3 stays trainable"""
+    return _image("mb", num_classes, transfer_learning, kw)
+
+
 def DistilBert(n_classes, drop_ratio, **kw):
     """text_models.py DistilBert: DistilBertModel (frozen), Dropout(drop_ratio), out = Linear(768, n_classes)"""
     return TextClassifier("distilbert", n_classes, drop_ratio, True, **kw)
@@ -239,5 +249,5 @@ def Roberta(n_classes, drop_ratio, **kw):
 
 
 IMAGE_FACTORIES = {"transformer_B16": VisionB16, "transformer_L16": VisionL16, "eff_v2_medium": EffNetV2_M, "eff_v2_large": EffNetV2_L,
-                   "shuffle_net": ShuffleNetV2}
+                   "shuffle_net": ShuffleNetV2, "mb": MBNetLarge}
 TEXT_FACTORIES = {"distilbert": DistilBert, "bert": Bert, "roberta": Roberta}

@@ -1,4 +1,5 @@
-"""Conv image backbones over libmmrca (csrc/conv.hip + the K2 GEMM): EfficientNetV2-M / -L and ShuffleNetV2 x2.0.
+"""Conv image backbones over libmmrca (csrc/conv.hip + the K2 GEMM): EfficientNetV2-M / -L, ShuffleNetV2 x2.0 and, for the
+single-modality classifiers only, MobileNetV3-Large.
 
 What this replaces in the reference: ``eff_net_v2()`` + ``EfficientNetV2MFullFeatureExtractor``
 (CVPR_code/multimodal_model.py:11-36, 113-126 -- the image model MM_RCA actually runs; ``main_both.py:259`` forces it) and, for
@@ -82,6 +83,31 @@ EFFNET_V2 = {
 }
 SHUFFLE_X2 = dict(repeats=[4, 8, 4], channels=[24, 244, 488, 976, 2048])       # shufflenet_v2_x2_0
 CONV_MODELS = {"eff_v2_medium": 1280, "EffNetv2-Medium": 1280, "eff_v2_large": 1280, "shuffle_net": 2048}
+# backbones of the single-modality classifiers only (classifier_engine.py): MM_RCA, MMRCAEngine and main_both.py consult CONV_MODELS
+# and keep treating these names as unknown image models
+CLASSIFIER_CONV_MODELS = {"mb": 1280}
+# (in, kernel, expanded, out, squeeze-excitation, activation, stride) -- torchvision/models/mobilenetv3.py, _mobilenet_v3_conf("mobilenet_v3_large")
+MBV3_LARGE = [(16, 3, 16, 16, False, "RE", 1), (16, 3, 64, 24, False, "RE", 2), (24, 3, 72, 24, False, "RE", 1),
+              (24, 5, 72, 40, True, "RE", 2), (40, 5, 120, 40, True, "RE", 1), (40, 5, 120, 40, True, "RE", 1),
+              (40, 3, 240, 80, False, "HS", 2), (80, 3, 200, 80, False, "HS", 1), (80, 3, 184, 80, False, "HS", 1),
+              (80, 3, 184, 80, False, "HS", 1), (80, 3, 480, 112, True, "HS", 1), (112, 3, 672, 112, True, "HS", 1),
+              (112, 5, 672, 160, True, "HS", 2), (160, 5, 960, 160, True, "HS", 1), (160, 5, 960, 160, True, "HS", 1)]
+MBV3_LAST, MBV3_TAIL = 960, 1280          # features.16 = 1x1 conv 160 -> 960; classifier.0 = Linear(960, 1280)
+
+
+def _make_divisible(v, divisor=8):
+    """torchvision.models._utils._make_divisible"""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    if new_v < 0.9 * v:
+        new_v += divisor
+    return new_v
+
+
+def mbv3_stage_of(n: int) -> str:
+    """gradient group of MobileNetV3-Large's features.n (n >= 1) -- one per output stride; features.16 and classifier.0 form the last"""
+    if n >= 16:
+        return "final_conv"
+    return "mb_s" + str(2 ** sum(1 for r in MBV3_LARGE[:n] if r[6] == 2) * 2)
 _ALIAS = {"EffNetv2-Medium": "eff_v2_medium"}
 
 
@@ -93,12 +119,13 @@ class _Unit:
     """conv (1x1 | 3x3 | depthwise 3x3, no bias) -> BatchNorm -> activation.  ``key`` is the torchvision prefix of the
     Conv2dNormActivation (conv = key.0, bn = key.1) or, for ShuffleNetV2's plain Sequentials, (conv key, bn key)."""
 
-    def __init__(self, conv_key, bn_key, cin, cout, k, stride, act, dw=False, eps=1e-3):
+    def __init__(self, conv_key, bn_key, cin, cout, k, stride, act, dw=False, eps=1e-3, momentum=0.1):
         self.conv_key, self.bn_key = conv_key, bn_key
         self.cin, self.cout, self.k, self.stride, self.act, self.dw, self.eps = cin, cout, k, stride, act, dw, eps
+        self.momentum = momentum            # BatchNorm running-statistics momentum (torchvision's MobileNetV3: 0.01)
 
     def params(self):
-        shp = (self.cout, 1, 3, 3) if self.dw else (self.cout, self.cin, self.k, self.k)
+        shp = (self.cout, 1, self.k, self.k) if self.dw else (self.cout, self.cin, self.k, self.k)
         return [(self.conv_key + ".weight", shp), (self.bn_key + ".weight", (self.cout,)), (self.bn_key + ".bias", (self.cout,))]
 
     def buffers(self):
@@ -107,8 +134,12 @@ class _Unit:
 
 
 class _SE:
-    def __init__(self, key, c, sq):
+    """squeeze-excitation: fc1 -> act1 -> fc2 -> act2 (EfficientNetV2: SiLU, sigmoid; MobileNetV3: ReLU, hard-sigmoid)"""
+
+    def __init__(self, key, c, sq, act1=None, act2=None):
         self.key, self.c, self.sq = key, c, sq
+        self.act1 = L.CONV_SILU if act1 is None else act1
+        self.act2 = L.CONV_SIGMOID if act2 is None else act2
 
     def params(self):
         return [(self.key + ".fc1.weight", (self.sq, self.c, 1, 1)), (self.key + ".fc1.bias", (self.sq,)),
@@ -121,14 +152,17 @@ class ConvEncoder:
 
     def __init__(self, name: str, owner, image_size: int = 224):
         name = _ALIAS.get(name, name)
-        if name not in ("eff_v2_medium", "eff_v2_large", "shuffle_net"):
+        if name not in ("eff_v2_medium", "eff_v2_large", "shuffle_net", "mb"):
             raise ValueError(f"Wrong image model: {name}")
         self.name, self.o, self.image = name, owner, image_size
-        self.dim = CONV_MODELS[name]
+        self.dim = CONV_MODELS[name] if name in CONV_MODELS else CLASSIFIER_CONV_MODELS[name]
         self.blocks: List[dict] = []          # execution plan
         self.sd_probs: List[float] = []
+        self.tail = None                      # MobileNetV3: classifier.0 (Linear 960 -> 1280 + hard-swish) behind the pooling
         if name == "shuffle_net":
             self._plan_shuffle()
+        elif name == "mb":
+            self._plan_mobilenet_v3()
         else:
             self._plan_effnet()
         self.buffers: Dict[str, torch.Tensor] = {}
@@ -197,6 +231,28 @@ class ConvEncoder:
             inp = oup
         self.final = U("conv5.0", "conv5.1", inp, ch[4], 1, 1, L.CONV_RELU)
 
+    def _plan_mobilenet_v3(self):
+        """torchvision mobilenet_v3_large: features.0 stem, features.1-15 inverted residual blocks ("mb" blocks: expand, depthwise,
+        squeeze-excitation, project), features.16 the last 1x1 convolution, classifier.0 the Linear of the tail.  BatchNorm eps 1e-3,
+        momentum 0.01; no stochastic depth."""
+        U = lambda ck, bk, ci, co, k, s, act, dw=False: _Unit(ck, bk, ci, co, k, s, act, dw, eps=1e-3, momentum=0.01)
+        act_of = {"RE": L.CONV_RELU, "HS": L.CONV_HSWISH}
+        self.stem = U("features.0.0", "features.0.1", 3, MBV3_LARGE[0][0], 3, 2, L.CONV_HSWISH)
+        for n, (cin, k, cexp, cout, se, a, stride) in enumerate(MBV3_LARGE, start=1):
+            P = f"features.{n}.block"
+            act = act_of[a]
+            blk = dict(kind="mb", res=(stride == 1 and cin == cout), sd=0.0, units=[], se=None, stage=mbv3_stage_of(n))
+            j = 0
+            if cexp != cin:
+                blk["units"].append(U(f"{P}.{j}.0", f"{P}.{j}.1", cin, cexp, 1, 1, act)); j += 1
+            blk["units"].append(U(f"{P}.{j}.0", f"{P}.{j}.1", cexp, cexp, k, stride, act, dw=True)); j += 1
+            if se:
+                blk["se"] = _SE(f"{P}.{j}", cexp, _make_divisible(cexp // 4, 8), L.CONV_RELU, L.CONV_HSIGMOID); j += 1
+            blk["units"].append(U(f"{P}.{j}.0", f"{P}.{j}.1", cexp, cout, 1, 1, L.CONV_NONE))
+            self.blocks.append(blk)
+        self.final = U("features.16.0", "features.16.1", MBV3_LARGE[-1][3], MBV3_LAST, 1, 1, L.CONV_HSWISH)
+        self.tail = ("classifier.0", MBV3_LAST, MBV3_TAIL, L.CONV_HSWISH)
+
     def _all_units(self):
         yield self.stem
         for b in self.blocks:
@@ -225,6 +281,9 @@ class ConvEncoder:
                 for u in b.get("b1", []) + b["b2"]:
                     unit(u)
         unit(self.final)
+        if self.tail is not None:
+            key, fin, fout, _ = self.tail
+            out += [(key + ".weight", (fout, fin)), (key + ".bias", (fout,))]
         return out
 
     def buffer_entries(self):
@@ -389,7 +448,9 @@ class ConvEncoder:
         fused_stats = False
         sums = None
         fold = False
-        if u.dw:
+        if u.dw and u.k == 5:
+            L.dwconv5x5_fwd(x, w, z, B, H, Wd, u.cin, u.stride, dt)
+        elif u.dw:
             L.dwconv3x3_fwd(x, w, z, B, H, Wd, u.cin, u.stride, dt)
         elif u.k == 1:
             if train and FUSE_GEMM_BN and self.o.gemm_impl == L.IMPL_AUTO and L.gemm_bnstats_ok(rows, u.cout, u.cin, dt):
@@ -424,9 +485,9 @@ class ConvEncoder:
         mean, rstd = stats[0], stats[1]
         rm, rv = self.buffers[u.bn_key + ".running_mean"], self.buffers[u.bn_key + ".running_var"]
         if fused_stats:
-            L.conv_bn_finish(parts, B, H, Wd, mean, rstd, rm, rv, u.cout, u.eps, 0.1)
+            L.conv_bn_finish(parts, B, H, Wd, mean, rstd, rm, rv, u.cout, u.eps, u.momentum)
         elif sums is not None:
-            L.bn_finish_sums(sums[0], sums[1], rm, sums[2], rows, mean, rstd, rm, rv, u.cout, u.eps, 0.1)
+            L.bn_finish_sums(sums[0], sums[1], rm, sums[2], rows, mean, rstd, rm, rv, u.cout, u.eps, u.momentum)
         else:
             fold = BN_FOLD and train and not BN_FLAT and not FUSE_BN_FINISH and L.bn_fold_ok(u.cout, u.cout, dt)
             if fold:
@@ -434,13 +495,13 @@ class ConvEncoder:
                 L.bn_moments(z, s1, s2, shift, rows, u.cout, u.cout, dt)
             else:
                 fuse = FUSE_BN_FINISH and train and self.cdtype == torch.bfloat16 and u.cout % 8 == 0 and not BN_FLAT
-                L.bn_stats(z, mean, rstd, rm, rv, rows, u.cout, u.cout, u.eps, 0.1 if train else 0.0, train, dt, ws=self._bn_ws(), prezeroed=True,
+                L.bn_stats(z, mean, rstd, rm, rv, rows, u.cout, u.cout, u.eps, u.momentum if train else 0.0, train, dt, ws=self._bn_ws(), prezeroed=True,
                            tickets=self._bn_tickets(u) if fuse else None)
         fused_res = res is not None and FUSE_RES and self.cdtype == torch.bfloat16 and u.cout % 8 == 0
         if fold:
             y = out if fused_res else self.buf(tag + ".y", rows, u.cout)
             L.bn_act_fwd_fin(z, s1, s2, shift, self.W(u.bn_key + ".weight"), self.W(u.bn_key + ".bias"), res if fused_res else None,
-                             rowscale if fused_res else None, y, mean, rstd, rm, rv, rows, u.cout, u.act, Ho * Wo, u.eps, 0.1, dt)
+                             rowscale if fused_res else None, y, mean, rstd, rm, rv, rows, u.cout, u.act, Ho * Wo, u.eps, u.momentum, dt)
         elif fused_res:
             y = out
             L.bn_act_fwd_res(z, mean, rstd, self.W(u.bn_key + ".weight"), self.W(u.bn_key + ".bias"), res, rowscale, y, rows, u.cout, u.act,
@@ -477,7 +538,8 @@ class ConvEncoder:
         return self._scratch("splitk", L.SPLITK_WS_BYTES, per_stream=True)
 
     def _dw_ws(self):
-        """partial sums of the depthwise weight gradient (csrc/conv.hip: at most 196,608 threads x 288 B, written before they are read)"""
+        """partial sums of the depthwise weight gradients (csrc/conv.hip, written before they are read): 3x3 at most 196,608 threads x
+        288 B; 5x5 at most 262,144 threads x 160 B + the fixed-order reduction's 16 x C x 100 B"""
         return self._scratch("dw", 64 << 20, per_stream=True).view(torch.float32)      # (per stream: MMRCA_CONV_SIDE_MAXROWS can leave some layers on the main one)
 
     def _side_on(self, rows: int) -> bool:
@@ -527,13 +589,15 @@ class ConvEncoder:
         rows_in = B * H * Wd
         dx = self.buf(f"{tag}.dx.{u.cin}.{rows_in}", rows_in, u.cin) if need_dx else None
         rows_k = _ru(rows, 64)                       # the contraction of the weight gradient runs over whole 64-row steps (zero pad rows)
-        if u.dw and SIDE_DW and self._side_on(rows):
-            # (the library runs the input gradient and the weight gradient as separate launches anyway: one call for each)
-            with self._wgrad_stream(dz_key, rows):
-                L.dwconv3x3_bwd(dz, sv["x"], w, None, gw, B, H, Wd, u.cin, u.stride, dt, ws=self._dw_ws())
-            L.dwconv3x3_bwd(dz, sv["x"], w, dx, None, B, H, Wd, u.cin, u.stride, dt)
-        elif u.dw:
-            L.dwconv3x3_bwd(dz, sv["x"], w, dx, gw, B, H, Wd, u.cin, u.stride, dt, ws=self._dw_ws())
+        if u.dw:
+            dw_bwd = L.dwconv5x5_bwd if u.k == 5 else L.dwconv3x3_bwd
+            if SIDE_DW and self._side_on(rows):
+                # (the library runs the input gradient and the weight gradient as separate launches anyway: one call for each)
+                with self._wgrad_stream(dz_key, rows):
+                    dw_bwd(dz, sv["x"], w, None, gw, B, H, Wd, u.cin, u.stride, dt, ws=self._dw_ws())
+                dw_bwd(dz, sv["x"], w, dx, None, B, H, Wd, u.cin, u.stride, dt)
+            else:
+                dw_bwd(dz, sv["x"], w, dx, gw, B, H, Wd, u.cin, u.stride, dt, ws=self._dw_ws())
         elif u.k == 1:
             with self._wgrad_stream(dz_key, rows):
                 if self._wgrad_slab(u.cout, u.cin, rows_k, dt):
@@ -598,7 +662,8 @@ class ConvEncoder:
         multiple of 8 (EfficientNetV2-M: 20 / 44 / 76 -> the general GEMM kernel).  Measured (tools/se_bench.py, us, fused vs GEMM
         sequence): forward 1824 x 76: 23 vs 75, 2304 x 96: 32 vs 44, 3072 x 128: 51 vs 46, 3840 x 160: 79 vs 62; backward 1824 x 76: 48 vs 137,
         2304 x 96: 76 vs 66.  Forward and backward choose independently (both forms save the same tensors)."""
-        return FUSE_SE_MLP and se.c % 4 == 0 and se.sq % 4 == 0 and (se.c * se.sq <= limit or se.sq % 8 != 0)
+        return (FUSE_SE_MLP and se.act1 == L.CONV_SILU and se.act2 == L.CONV_SIGMOID and se.c % 4 == 0 and se.sq % 4 == 0
+                and (se.c * se.sq <= limit or se.sq % 8 != 0))
 
     def _se_fwd(self, se: _SE, x, B, HW, tag, save):
         dt = self.cdt
@@ -611,9 +676,9 @@ class ConvEncoder:
                          self.W(se.key + ".fc2.bias"), h_pre, h, s_pre, s, B, se.c, se.sq, dt)
         else:
             L.gemm(pooled, self.W(se.key + ".fc1.weight"), h_pre, M=B, N=se.sq, K=se.c, lda=se.c, ldb=se.c, ldc=se.sq, dtype=dt, impl=self.o.gemm_impl)
-            L.bias_act_fwd(h_pre, self.W(se.key + ".fc1.bias"), h, B, se.sq, L.CONV_SILU, dt)
+            L.bias_act_fwd(h_pre, self.W(se.key + ".fc1.bias"), h, B, se.sq, se.act1, dt)
             L.gemm(h, self.W(se.key + ".fc2.weight"), s_pre, M=B, N=se.c, K=se.sq, lda=se.sq, ldb=se.sq, ldc=se.c, dtype=dt, impl=self.o.gemm_impl)
-            L.bias_act_fwd(s_pre, self.W(se.key + ".fc2.bias"), s, B, se.c, L.CONV_SIGMOID, dt)
+            L.bias_act_fwd(s_pre, self.W(se.key + ".fc2.bias"), s, B, se.c, se.act2, dt)
         y = self.buf(tag + ".se.y", B * HW, se.c)
         L.se_scale_fwd(x, s, y, B, HW, se.c, dt)
         return y, dict(x=x, pooled=pooled, h_pre=h_pre, h=h, s_pre=s_pre, s=s, HW=HW)
@@ -633,14 +698,14 @@ class ConvEncoder:
                          self.W(se.key + ".fc2.weight"), self.W(se.key + ".fc2.bias"), ds_pre, dh_pre, dpool, self.G(se.key + ".fc1.weight"),
                          self.G(se.key + ".fc1.bias"), self.G(se.key + ".fc2.weight"), self.G(se.key + ".fc2.bias"), B, se.c, se.sq, dt)
         else:
-            L.bias_act_bwd(ds, sv["s_pre"], self.W(se.key + ".fc2.bias"), ds_pre, self.G(se.key + ".fc2.bias"), B, se.c, L.CONV_SIGMOID, dt)
+            L.bias_act_bwd(ds, sv["s_pre"], self.W(se.key + ".fc2.bias"), ds_pre, self.G(se.key + ".fc2.bias"), B, se.c, se.act2, dt)
             Bk = _ru(B, 64)
             L.gemm(ds_pre, sv["h"], self.G(se.key + ".fc2.weight"), M=se.c, N=se.sq, K=Bk, lda=se.c, ldb=se.sq, ldc=se.sq, a_layout=L.KROW,
                    b_layout=L.KROW, accum=True, dtype=dt, impl=self.o.gemm_impl)
             dh = g(".dh", B, se.sq)
             L.gemm(ds_pre, self.W(se.key + ".fc2.weight"), dh, M=B, N=se.sq, K=se.c, lda=se.c, ldb=se.sq, ldc=se.sq, a_layout=L.ROWK, b_layout=L.KROW,
                    dtype=dt, impl=self.o.gemm_impl)
-            L.bias_act_bwd(dh, sv["h_pre"], self.W(se.key + ".fc1.bias"), dh_pre, self.G(se.key + ".fc1.bias"), B, se.sq, L.CONV_SILU, dt)
+            L.bias_act_bwd(dh, sv["h_pre"], self.W(se.key + ".fc1.bias"), dh_pre, self.G(se.key + ".fc1.bias"), B, se.sq, se.act1, dt)
             L.gemm(dh_pre, sv["pooled"], self.G(se.key + ".fc1.weight"), M=se.sq, N=se.c, K=Bk, lda=se.sq, ldb=se.c, ldc=se.c, a_layout=L.KROW,
                    b_layout=L.KROW, accum=True, dtype=dt, impl=self.o.gemm_impl)
             L.gemm(dh_pre, self.W(se.key + ".fc1.weight"), dpool, M=B, N=se.c, K=se.sq, lda=se.sq, ldb=se.c, ldc=se.c, a_layout=L.ROWK, b_layout=L.KROW,
@@ -753,11 +818,39 @@ class ConvEncoder:
                 x = self._shuffle_cat(x, y2, rows, Cc, f"{tag}.out", first_is_full=True)
             saved["blocks"].append(bs)
         y, h, w, saved["final"] = self._unit_fwd(self.final, x, B, h, w, "final", train, save)
-        feat = self.buf("feat", B, self.dim)
-        L.rowpool_mean(y, feat, B, h * w, self.dim, dt)
         saved["HW"] = h * w
+        if self.tail is not None:
+            feat = self._tail_fwd(y, B, h * w, saved)
+        else:
+            feat = self.buf("feat", B, self.dim)
+            L.rowpool_mean(y, feat, B, h * w, self.dim, dt)
         self.saved = saved if save else None
         return feat[:B]
+
+    def _tail_fwd(self, y, B, HW, saved):
+        """MobileNetV3's classifier.0: pooled [B, 960] -> Linear + hard-swish -> feature [B, 1280] (the SE's GEMM + bias_act pair)"""
+        dt = self.cdt
+        key, fin, fout, act = self.tail
+        pooled, pre, feat = self.buf("tail.pool", B, fin), self.buf("tail.pre", B, fout), self.buf("feat", B, fout)
+        L.rowpool_mean(y, pooled, B, HW, fin, dt)
+        L.gemm(pooled, self.W(key + ".weight"), pre, M=B, N=fout, K=fin, lda=fin, ldb=fin, ldc=fout, dtype=dt, impl=self.o.gemm_impl)
+        L.bias_act_fwd(pre, self.W(key + ".bias"), feat, B, fout, act, dt)
+        saved["tail"] = dict(pooled=pooled, pre=pre)
+        return feat
+
+    def _tail_bwd(self, dfeat, sv, B):
+        """-> the gradient of the pooled final-convolution output [B, 960]; classifier.0's weight / bias gradients accumulated"""
+        dt = self.cdt
+        key, fin, fout, act = self.tail
+        tv = sv["tail"]
+        dfe, dpre, dpool = self.buf("g.dfeat", B, fout), self.buf("g.tail.dpre", B, fout), self.buf("g.dpool", B, fin)
+        dfe[:B].copy_(dfeat.to(dfe.dtype))
+        L.bias_act_bwd(dfe, tv["pre"], self.W(key + ".bias"), dpre, self.G(key + ".bias"), B, fout, act, dt)
+        L.gemm(dpre, tv["pooled"], self.G(key + ".weight"), M=fout, N=fin, K=_ru(B, 64), lda=fout, ldb=fin, ldc=fin, a_layout=L.KROW,
+               b_layout=L.KROW, accum=True, dtype=dt, impl=self.o.gemm_impl)
+        L.gemm(dpre, self.W(key + ".weight"), dpool, M=B, N=fin, K=fout, lda=fout, ldb=fin, ldc=fin, a_layout=L.ROWK, b_layout=L.KROW,
+               dtype=dt, impl=self.o.gemm_impl)
+        return dpool
 
     def _shuffle_cat(self, a, b, rows, Cc, name, first_is_full=False):
         """channel_shuffle(cat(a', b), groups=2): out[:, 2j] = a'[:, j], out[:, 2j+1] = b[:, j]  (a' = first half of a when
@@ -787,10 +880,14 @@ class ConvEncoder:
         dt = self.cdt
         B = sv["B"]
         HW = sv["HW"]
-        dpool = self.buf("g.dfeat", B, self.dim)
-        dpool[:B].copy_(dfeat.to(dpool.dtype))
-        dy = self.buf("g.dfinal", B * HW, self.dim)
-        L.rowpool_mean_bwd(dpool, dy, B, HW, self.dim, False, dt)
+        if self.tail is not None:
+            dpool = self._tail_bwd(dfeat, sv, B)
+        else:
+            dpool = self.buf("g.dfeat", B, self.dim)
+            dpool[:B].copy_(dfeat.to(dpool.dtype))
+        cf = self.final.cout
+        dy = self.buf("g.dfinal", B * HW, cf)
+        L.rowpool_mean_bwd(dpool, dy, B, HW, cf, False, dt)
         dx = self._unit_bwd(self.final, dy, sv["final"], B)
         # the gradients of a stage are final once its first block's backward is queued: hand them to the data-parallel exchange
         # stage by stage (engine._ready -> GradSync.span_ready), so that it overlaps the backward of the stages below

@@ -6,8 +6,8 @@
 //   * a full 3x3 convolution is mmrca_im2row3x3 + mmrca_gemm: the patch row is channel-major, col[c*9 + ky*3 + kx], which is
 //     exactly the flattening of torchvision's [Cout, Cin, 3, 3] weight -- no re-laid weight copy exists; its input gradient is
 //     mmrca_gemm (dcol = dz W) + mmrca_col2im3x3 (a gather over the <= 9 output pixels that read an input pixel: no atomics);
-//   * depthwise 3x3, BatchNorm (batch statistics in training, running statistics in eval, running-stat update), SiLU / ReLU /
-//     sigmoid, squeeze-excitation pooling and scaling, stochastic depth, 3x3/2 max pooling are the kernels below.
+//   * depthwise 3x3 and 5x5, BatchNorm (batch statistics in training, running statistics in eval, running-stat update), SiLU / ReLU /
+//     sigmoid / hard-swish / hard-sigmoid, squeeze-excitation pooling and scaling, stochastic depth, 3x3/2 max pooling are the kernels below.
 // Everything here is HBM-bound elementwise / reduction work: one thread per (pixel, channel) with the channel index
 // fastest (coalesced), fp32 arithmetic, fp32 statistics and parameter gradients.
 #include "common.h"
@@ -16,12 +16,17 @@
 #define CONV_ACT_SILU 1
 #define CONV_ACT_RELU 2
 #define CONV_ACT_SIGMOID 3
+#define CONV_ACT_HSWISH 4           // MobileNetV3: u * min(max(u + 3, 0), 6) / 6 (torch.nn.Hardswish)
+#define CONV_ACT_HSIGMOID 5         // min(max(u + 3, 0), 6) / 6 (torch.nn.Hardsigmoid)
 
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   // (hardware reciprocal, 1 ulp: an IEEE division is ten instructions per element in the BatchNorm passes)
 __device__ __forceinline__ float act_f(float u, int act) {
   if (act == CONV_ACT_SILU) return u * sigmoid_f(u);
   if (act == CONV_ACT_RELU) return u > 0.f ? u : 0.f;
   if (act == CONV_ACT_SIGMOID) return sigmoid_f(u);
+  // (products with 1/6: no IEEE division in the per-element code)
+  if (act == CONV_ACT_HSWISH) return u * fminf(fmaxf(u + 3.f, 0.f), 6.f) * (1.f / 6.f);
+  if (act == CONV_ACT_HSIGMOID) return fminf(fmaxf(u + 3.f, 0.f), 6.f) * (1.f / 6.f);
   return u;
 }
 // d act(u) / du
@@ -29,8 +34,24 @@ __device__ __forceinline__ float act_grad_f(float u, int act) {
   if (act == CONV_ACT_SILU) { const float s = sigmoid_f(u); return s * (1.0f + u * (1.0f - s)); }
   if (act == CONV_ACT_RELU) return u > 0.f ? 1.f : 0.f;
   if (act == CONV_ACT_SIGMOID) { const float s = sigmoid_f(u); return s * (1.0f - s); }
+  // aten's conventions at the kinks (torch 2.x hardswish_backward / hardsigmoid_backward): both slopes on the open interval (-3, 3),
+  // hardswish' = 0 at -3 and 1 at +3
+  if (act == CONV_ACT_HSWISH) return u <= -3.f ? 0.f : (u < 3.f ? fmaf(u, 1.f / 3.f, 0.5f) : 1.f);
+  if (act == CONV_ACT_HSIGMOID) return (u > -3.f && u < 3.f) ? 1.f / 6.f : 0.f;
   return 1.f;
 }
+
+// Activation code -> template argument of the kernels that apply one per element (ACT = -1: the run-time code).  With the code a
+// run-time argument every unrolled element carried its own chain of uniform branches, and each code added lengthened it for all.
+#define CONV_ACT_SWITCH(act, ...)                                                                                                     \
+  switch (act) {                                                                                                                     \
+    case 0: { constexpr int ACT = 0; __VA_ARGS__ } break;                                                                            \
+    case 1: { constexpr int ACT = 1; __VA_ARGS__ } break;                                                                            \
+    case 2: { constexpr int ACT = 2; __VA_ARGS__ } break;                                                                            \
+    case 3: { constexpr int ACT = 3; __VA_ARGS__ } break;                                                                            \
+    case 4: { constexpr int ACT = 4; __VA_ARGS__ } break;                                                                            \
+    default: { constexpr int ACT = 5; __VA_ARGS__ } break;                                                                           \
+  }
 
 static inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
@@ -1076,6 +1097,491 @@ extern "C" int mmrca_dwconv3x3_bwd_ws(const void* dy, const void* x, const void*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// depthwise 5x5, padding 2, stride 1 or 2 (MobileNetV3-Large: 72 / 120 / 672 / 960 channels).  w: [C, 25] in `dtype`
+// (torchvision's [C, 1, 5, 5]); dw: fp32 [C, 25], +=.
+//   * generic kernels (fp32 and bf16, any C): one thread per (pixel, channel), 64-bit indices;
+//   * bf16, C % 8 == 0, 16-byte aligned: 8 channels per thread and 16-byte loads.  The thread's 200 weights stay packed
+//     (25 sixteen-byte vectors, 100 registers) and one kernel row of them (40 floats) is converted at a time: 200 fp32 weights
+//     next to the window and the sums did not fit.  Every load of a window row is issued before the row is used (clamped
+//     addresses, out-of-image values zeroed afterwards); indices are 32-bit unless a tensor has 2^31 elements or more.
+//   * the weight gradient streams dy and x front to back: thread = (pixel lane, kernel row, 8-channel group), 40 sums each, written
+//     to the workspace and added up in a fixed order (bitwise reproducible); without a workspace, fp32 atomics.
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void dwconv5x5_fwd_k(const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ y, int B, int H, int W, int C,
+                                int Ho, int Wo, int stride) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * Ho * Wo * C) return;
+  const int c = (int)(idx % C);
+  const int64_t op = idx / C;
+  const int ox = (int)(op % Wo), oy = (int)((op / Wo) % Ho), b = (int)(op / ((int64_t)Wo * Ho));
+  float s = 0.f;
+#pragma unroll
+  for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) {
+      const int iy = oy * stride + ky - 2, ix = ox * stride + kx - 2;
+      if (iy >= 0 && iy < H && ix >= 0 && ix < W) s = fmaf(to_f(x[(((int64_t)b * H + iy) * W + ix) * C + c]), to_f(w[(int64_t)c * 25 + ky * 5 + kx]), s);
+    }
+  y[idx] = from_f<T>(s);
+}
+
+template <typename T>
+__global__ void dwconv5x5_bwd_data_k(const T* __restrict__ dy, const T* __restrict__ w, T* __restrict__ dx, int B, int H, int W, int C,
+                                     int Ho, int Wo, int stride) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)B * H * W * C) return;
+  const int c = (int)(idx % C);
+  const int64_t ip = idx / C;
+  const int ix = (int)(ip % W), iy = (int)((ip / W) % H), b = (int)(ip / ((int64_t)W * H));
+  float s = 0.f;
+#pragma unroll
+  for (int ky = 0; ky < 5; ++ky) {
+    const int ty = iy + 2 - ky;
+    if (ty < 0 || ty % stride) continue;
+    const int oy = ty / stride;
+    if (oy >= Ho) continue;
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) {
+      const int tx = ix + 2 - kx;
+      if (tx < 0 || tx % stride) continue;
+      const int ox = tx / stride;
+      if (ox >= Wo) continue;
+      s = fmaf(to_f(dy[(((int64_t)b * Ho + oy) * Wo + ox) * C + c]), to_f(w[(int64_t)c * 25 + ky * 5 + kx]), s);
+    }
+  }
+  dx[idx] = from_f<T>(s);
+}
+
+// block = 64 channels x 4 pixel lanes over one pixel range (grid.y); the lanes meet in LDS in a fixed order.  WS: the block's sums
+// go to row blockIdx.y of the workspace ([ranges, C * 25]); otherwise one atomic per (channel, tap) and block.
+template <typename T, bool WS>
+__global__ void __launch_bounds__(256)
+dwconv5x5_bwd_weight_k(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ dw, int B, int H, int W, int C, int Ho, int Wo,
+                       int stride, int64_t pix_per_block, float* __restrict__ ws) {
+  __shared__ float red[4][64][25];
+  const int cl = threadIdx.x & 63, pl = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cl;
+  float acc[25];
+#pragma unroll
+  for (int t = 0; t < 25; ++t) acc[t] = 0.f;
+  const int64_t npix = (int64_t)B * Ho * Wo;
+  const int64_t p0 = (int64_t)blockIdx.y * pix_per_block;
+  const int64_t p1 = p0 + pix_per_block < npix ? p0 + pix_per_block : npix;
+  if (c < C) {
+    for (int64_t op = p0 + pl; op < p1; op += 4) {
+      const int ox = (int)(op % Wo), oy = (int)((op / Wo) % Ho), b = (int)(op / ((int64_t)Wo * Ho));
+      const float g = to_f(dy[op * C + c]);
+#pragma unroll
+      for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 5; ++kx) {
+          const int iy = oy * stride + ky - 2, ix = ox * stride + kx - 2;
+          if (iy >= 0 && iy < H && ix >= 0 && ix < W) acc[ky * 5 + kx] = fmaf(g, to_f(x[(((int64_t)b * H + iy) * W + ix) * C + c]), acc[ky * 5 + kx]);
+        }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 25; ++t) red[pl][cl][t] = acc[t];
+  __syncthreads();
+  if (pl == 0 && c < C) {
+#pragma unroll
+    for (int t = 0; t < 25; ++t) {
+      const float v = (red[0][cl][t] + red[1][cl][t]) + (red[2][cl][t] + red[3][cl][t]);
+      if (WS) ws[(int64_t)blockIdx.y * C * 25 + (int64_t)c * 25 + t] = v;
+      else atomicAdd(dw + (int64_t)c * 25 + t, v);
+    }
+  }
+}
+
+// ---- bf16, 8 channels per thread
+__device__ __forceinline__ void dw5_load_w8(const bf16_t* __restrict__ w, int64_t c0, cv_b8 (&wv)[25]) {
+  const cv_b8* p = reinterpret_cast<const cv_b8*>(w + c0 * 25);      // w[c0*25 .. c0*25+199], 16-byte aligned (c0 % 8 == 0)
+#pragma unroll
+  for (int i = 0; i < 25; ++i) wv[i] = p[i];
+}
+
+// kernel row ky of the thread's 8 channels as floats: wr[j][kx] = w[c0 + j][ky * 5 + kx] (FLIP: w[c0 + j][24 - ky * 5 - kx])
+template <bool FLIP>
+__device__ __forceinline__ void dw5_row_w8(const cv_b8 (&wv)[25], int ky, float (&wr)[8][5]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) {
+      const int e = j * 25 + (FLIP ? 24 - ky * 5 - kx : ky * 5 + kx);
+      wr[j][kx] = (float)wv[e / 8][e % 8];
+    }
+}
+
+__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// Forward (FLIP = false) and the stride-1 input gradient (FLIP = true: the same correlation with the kernel turned by 180 degrees;
+// padding 2 = 5 - 1 - 2 on both sides).  A thread owns ONE output pixel for its 8 channels: 85 (forward, stride 1) / 120 registers,
+// four or five waves per SIMD, the 5 loads of a window row issued together (neighbouring threads' windows overlap in L1 / L2).  Two
+// or four outputs per thread, as the 3x3 strip kernels do, made the compiler keep the 200 weights converted to fp32 next to the
+// wider window: 413 / 457 registers (arch + accumulation VGPRs), one wave per SIMD.
+template <int S, bool FLIP, typename I>
+__global__ void __launch_bounds__(256)
+dw5x5_fwd_v8_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, bf16_t* __restrict__ y, int B, int H, int W, int C, int Ho, int Wo) {
+  const I C8 = (I)(C >> 3);
+  const I idx = (I)xcd_block() * 256u + threadIdx.x;
+  if (idx >= (I)B * (I)Ho * (I)Wo * C8) return;
+  const I c0 = (idx % C8) * 8;
+  I g = idx / C8;
+  const int ox = (int)(g % (I)Wo);
+  g /= (I)Wo;
+  const int oy = (int)(g % (I)Ho);
+  const I b = g / (I)Ho;
+  cv_b8 wv[25];
+  dw5_load_w8(w, (int64_t)c0, wv);
+  I coff[5];
+  bool cvd[5];
+#pragma unroll
+  for (int kx = 0; kx < 5; ++kx) {
+    const int ix = ox * S + kx - 2;
+    cvd[kx] = ix >= 0 && ix < W;
+    coff[kx] = (I)clampi(ix, W - 1) * (I)C;
+  }
+  float s[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s[j] = 0.f;
+#pragma unroll
+  for (int ky = 0; ky < 5; ++ky) {
+    const int iy = oy * S + ky - 2;
+    const bool rv = iy >= 0 && iy < H;
+    const I rowoff = ((b * (I)H + (I)clampi(iy, H - 1)) * (I)W) * (I)C + c0;
+    cv_b8 v[5];
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) v[kx] = *reinterpret_cast<const cv_b8*>(x + (rowoff + coff[kx]));
+    float wr[8][5];
+    dw5_row_w8<FLIP>(wv, ky, wr);
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) {
+      const bool ok = rv && cvd[kx];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s[j] = fmaf(ok ? (float)v[kx][j] : 0.f, wr[j][kx], s[j]);
+    }
+  }
+  cv_b8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = (bf16_t)s[j];
+  *reinterpret_cast<cv_b8*>(y + (((b * (I)Ho + (I)oy) * (I)Wo + (I)ox) * (I)C + c0)) = r;
+}
+
+// Stride-2 input gradient: dx[iy, ix] = sum of dy[(iy + 2 - ky) / 2, (ix + 2 - kx) / 2] w[ky, kx] over the taps whose offsets are
+// even.  A thread owns the input pixels (iy, 2q) and (iy, 2q + 1): both read the 3 x 3 dy window at rows iy / 2 - 1 + r and columns
+// q - 1 + c; the even column takes kx = 4 - 2c, the odd one kx = 5 - 2c (c >= 1), and the rows ky = 4 - 2r (iy even) or 5 - 2r
+// (iy odd, r >= 1) -- 9 loads for two pixels.
+template <int PY>
+__device__ __forceinline__ void dw5_s2_data_acc(const float (&v)[3][3][8], const cv_b8 (&wv)[25], float (&s)[2][8]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int ky = PY ? 5 - 2 * r : 4 - 2 * r;
+    if (ky > 4) continue;
+    float wr[8][5];
+    dw5_row_w8<false>(wv, ky, wr);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int px = 0; px < 2; ++px) {
+        const int kx = px ? 5 - 2 * c : 4 - 2 * c;
+        if (kx > 4) continue;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[px][j] = fmaf(v[r][c][j], wr[j][kx], s[px][j]);
+      }
+    }
+  }
+}
+
+template <typename I>
+__global__ void __launch_bounds__(256)
+dw5x5_s2_data_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ w, bf16_t* __restrict__ dx, int B, int H, int W, int C, int Ho,
+                   int Wo) {
+  const I C8 = (I)(C >> 3), XG = (I)((W + 1) >> 1);
+  const I idx = (I)xcd_block() * 256u + threadIdx.x;
+  if (idx >= (I)B * (I)H * XG * C8) return;
+  const I c0 = (idx % C8) * 8;
+  I g = idx / C8;
+  const int q = (int)(g % XG);
+  g /= XG;
+  const int iy = (int)(g % (I)H);
+  const I b = g / (I)H;
+  cv_b8 raw[3][3];
+  bool rv[3], cvd[3];
+  I coff[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int ox = q - 1 + c;
+    cvd[c] = ox >= 0 && ox < Wo;
+    coff[c] = (I)clampi(ox, Wo - 1) * (I)C;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int oy = (iy >> 1) - 1 + r;
+    rv[r] = oy >= 0 && oy < Ho;
+    const I rowoff = ((b * (I)Ho + (I)clampi(oy, Ho - 1)) * (I)Wo) * (I)C + c0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) raw[r][c] = *reinterpret_cast<const cv_b8*>(dy + (rowoff + coff[c]));
+  }
+  cv_b8 wv[25];
+  dw5_load_w8(w, (int64_t)c0, wv);
+  float v[3][3][8];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[r][c][j] = (rv[r] && cvd[c]) ? (float)raw[r][c][j] : 0.f;
+  float s[2][8];
+#pragma unroll
+  for (int px = 0; px < 2; ++px)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[px][j] = 0.f;
+  if (iy & 1) dw5_s2_data_acc<1>(v, wv, s);
+  else dw5_s2_data_acc<0>(v, wv, s);
+#pragma unroll
+  for (int px = 0; px < 2; ++px) {
+    const int ix = 2 * q + px;
+    if (ix >= W) continue;
+    cv_b8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (bf16_t)s[px][j];
+    *reinterpret_cast<cv_b8*>(dx + (((b * (I)H + (I)iy) * (I)W + (I)ix) * (I)C + c0)) = r;
+  }
+}
+
+// Streaming weight gradient: thread tid = (lane * 5 + ky) * C8 + c8 keeps the 40 sums of kernel row ky for its 8 channels and walks
+// the pixel groups (one output row x 4 output pixels) g = lane, lane + lanes, ...: consecutive threads read consecutive 16-byte chunks,
+// and at any moment the resident threads cover consecutive pixel groups over all channels.  WS: the sums go to row `lane` of the
+// workspace ([lanes, C * 25]); otherwise fp32 atomics.
+template <int S, bool WS, typename I>
+__global__ void __launch_bounds__(256)
+dw5x5_wgrad_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ dw, int B, int H, int W, int C, int Ho, int Wo,
+                 unsigned lanes, float* __restrict__ ws) {
+  constexpr int OPX = 4, WC = (OPX - 1) * S + 5;
+  const unsigned C8 = (unsigned)C >> 3;
+  const unsigned tid = blockIdx.x * 256u + threadIdx.x;
+  if (tid >= lanes * 5u * C8) return;
+  const unsigned c8 = tid % C8, ky = (tid / C8) % 5u, lane = tid / (C8 * 5u);
+  const I c0 = (I)c8 * 8;
+  const unsigned XG = ((unsigned)Wo + OPX - 1) / OPX, ngrp = (unsigned)B * (unsigned)Ho * XG;
+  float acc[8][5];
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) acc[j][kx] = 0.f;
+  for (unsigned g = lane; g < ngrp; g += lanes) {
+    const int ox0 = (int)(g % XG) * OPX;
+    const unsigned t = g / XG;
+    const int oy = (int)(t % (unsigned)Ho);
+    const I b = (I)(t / (unsigned)Ho);
+    const int iy = oy * S + (int)ky - 2;
+    const bool rv = iy >= 0 && iy < H;
+    cv_b8 gvb[OPX], xv[WC];
+    bool gok[OPX], cvd[WC];
+    const I drow = ((b * (I)Ho + (I)oy) * (I)Wo) * (I)C + c0;
+#pragma unroll
+    for (int o = 0; o < OPX; ++o) {
+      gok[o] = ox0 + o < Wo;
+      gvb[o] = *reinterpret_cast<const cv_b8*>(dy + (drow + (I)clampi(ox0 + o, Wo - 1) * (I)C));
+    }
+    const I xrow = ((b * (I)H + (I)clampi(iy, H - 1)) * (I)W) * (I)C + c0;
+#pragma unroll
+    for (int col = 0; col < WC; ++col) {
+      const int ix = ox0 * S + col - 2;
+      cvd[col] = rv && ix >= 0 && ix < W;
+      xv[col] = *reinterpret_cast<const cv_b8*>(x + (xrow + (I)clampi(ix, W - 1) * (I)C));
+    }
+    float gv[OPX][8];
+#pragma unroll
+    for (int o = 0; o < OPX; ++o)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) gv[o][j] = gok[o] ? (float)gvb[o][j] : 0.f;
+#pragma unroll
+    for (int col = 0; col < WC; ++col) {
+      float xf[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) xf[j] = cvd[col] ? (float)xv[col][j] : 0.f;
+#pragma unroll
+      for (int o = 0; o < OPX; ++o) {
+        const int kx = col - o * S;
+        if (kx < 0 || kx > 4) continue;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j][kx] = fmaf(gv[o][j], xf[j], acc[j][kx]);
+      }
+    }
+  }
+  const int64_t base = (int64_t)(c8 * 8) * 25 + ky * 5;
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+#pragma unroll
+    for (int kx = 0; kx < 5; ++kx) {
+      if (WS) ws[(int64_t)lane * C * 25 + base + j * 25 + kx] = acc[j][kx];
+      else atomicAdd(dw + base + j * 25 + kx, acc[j][kx]);
+    }
+}
+
+// dw[i] += sum over the rows of ws[row][i] in a fixed order: pass 1 = chunk sums (grid.y chunks of rows, 4 row lanes per output,
+// combined as (l0 + l1) + (l2 + l3)), pass 2 = the chunk sums in chunk order.  No atomics: the same launch sums the same bits.
+constexpr int DW5_RED_CHUNKS = 16;
+__global__ void __launch_bounds__(256)
+dw5_reduce_part_k(const float* __restrict__ ws, float* __restrict__ part, int nrows, int n) {
+  __shared__ float red[4][64];
+  const int il = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + il;
+  const int per = (nrows + gridDim.y - 1) / gridDim.y;
+  const int r0 = blockIdx.y * per, r1 = r0 + per < nrows ? r0 + per : nrows;
+  float s = 0.f;
+  if (i < n) {
+    int r = r0 + rl;
+    for (; r + 12 < r1; r += 16) {
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = ws[(int64_t)(r + 4 * u) * n + i];
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    for (; r < r1; r += 4) s += ws[(int64_t)r * n + i];
+  }
+  red[rl][il] = s;
+  __syncthreads();
+  if (rl == 0 && i < n) part[(int64_t)blockIdx.y * n + i] = (red[0][il] + red[1][il]) + (red[2][il] + red[3][il]);
+}
+
+__global__ void dw5_reduce_fin_k(const float* __restrict__ part, float* __restrict__ dw, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < DW5_RED_CHUNKS; ++k) s += part[(int64_t)k * n + i];
+  dw[i] += s;
+}
+
+static void dw5_reduce(const float* ws, int nrows, int n, float* part, float* dw, hipStream_t st) {
+  hipLaunchKernelGGL(dw5_reduce_part_k, dim3((unsigned)((n + 63) / 64), DW5_RED_CHUNKS), dim3(256), 0, st, ws, part, nrows, n);
+  hipLaunchKernelGGL(dw5_reduce_fin_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)part, dw, n);
+}
+
+// the largest element offset of a [B, H, W, C] tensor fits 32 bits (and so does every clamped address computed from it)
+static bool dw5_small32(int B, int H, int W, int C) { return (int64_t)B * H * W * C < (1ll << 31); }
+
+// threads of the streaming weight gradient: at most what is resident at once (108-122 registers: 4 waves per SIMD on 256 CUs), and
+// at least DW5_WG_MIN_GROUPS pixel groups per lane.  A lane's workspace row (C x 25 fp32) is written once and read back once: 200 C
+// bytes against the ~16 C (stride 1) / ~24 C (stride 2) bytes of dy and x per pixel group, so 32 groups keep the workspace traffic
+// under 40 % / 26 % of the algorithmic bytes (B = 256, 10 x 10, C = 960: 240 lanes, 23 MB of workspace instead of 64 MiB).
+static const int64_t DW5_WG_THREADS = 256 * 4 * 4 * 64;
+constexpr int64_t DW5_WG_MIN_GROUPS = 32;
+
+extern "C" int mmrca_dwconv5x5_fwd(const void* x, const void* w, void* y, int B, int H, int W, int C, int stride, int dtype, void* stream) {
+  MMRCA_REQUIRE(x && w && y && B > 0 && H > 0 && W > 0 && C > 0 && (stride == 1 || stride == 2), "dwconv5x5_fwd: bad arguments");
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (dw_v8_ok(C, dtype, x, w, y)) {
+    const bool s32 = dw5_small32(B, H, W, C);
+    const int64_t n = (int64_t)B * Ho * Wo * (C / 8);
+    const dim3 grid(blocks_for(n, 256));
+    if (stride == 1 && s32)
+      hipLaunchKernelGGL((dw5x5_fwd_v8_k<1, false, unsigned>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, B, H, W, C, Ho, Wo);
+    else if (stride == 1)
+      hipLaunchKernelGGL((dw5x5_fwd_v8_k<1, false, uint64_t>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, B, H, W, C, Ho, Wo);
+    else if (s32)
+      hipLaunchKernelGGL((dw5x5_fwd_v8_k<2, false, unsigned>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, B, H, W, C, Ho, Wo);
+    else
+      hipLaunchKernelGGL((dw5x5_fwd_v8_k<2, false, uint64_t>), grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, B, H, W, C, Ho, Wo);
+    MMRCA_CHECK_LAUNCH("dwconv5x5_fwd(v8)");
+    return 0;
+  }
+  const int64_t n = (int64_t)B * Ho * Wo * C;
+  MMRCA_DISPATCH_DTYPE(dtype, "dwconv5x5_fwd",
+    hipLaunchKernelGGL(dwconv5x5_fwd_k<T>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const T*)x, (const T*)w, (T*)y, B, H, W, C, Ho, Wo, stride);)
+  MMRCA_CHECK_LAUNCH("dwconv5x5_fwd");
+  return 0;
+}
+
+/* dx (may be NULL) and dw (fp32, +=, may be NULL).  ws (may be NULL): the weight gradient's partial sums, added in a fixed order
+ * (bitwise reproducible); a workspace too small for one pixel lane per 8-channel group falls back to the atomic form. */
+extern "C" int mmrca_dwconv5x5_bwd_ws(const void* dy, const void* x, const void* w, void* dx, float* dw, int B, int H, int W, int C, int stride,
+                                      int dtype, void* ws, int64_t ws_bytes, void* stream) {
+  MMRCA_REQUIRE(dy && x && w && B > 0 && H > 0 && W > 0 && C > 0 && (stride == 1 || stride == 2), "dwconv5x5_bwd: bad arguments");
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  hipStream_t st = (hipStream_t)stream;
+  const bool s32 = dw5_small32(B, H, W, C);
+  if (dx && dw_v8_ok(C, dtype, dy, w, dx)) {
+    if (stride == 1) {
+      const int64_t n = (int64_t)B * H * W * (C / 8);
+      if (s32)
+        hipLaunchKernelGGL((dw5x5_fwd_v8_k<1, true, unsigned>), dim3(blocks_for(n, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w,
+                           (bf16_t*)dx, B, H, W, C, H, W);
+      else
+        hipLaunchKernelGGL((dw5x5_fwd_v8_k<1, true, uint64_t>), dim3(blocks_for(n, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w,
+                           (bf16_t*)dx, B, H, W, C, H, W);
+    } else {
+      const int64_t n = (int64_t)B * H * ((W + 1) / 2) * (C / 8);
+      if (s32)
+        hipLaunchKernelGGL(dw5x5_s2_data_v8_k<unsigned>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx,
+                           B, H, W, C, Ho, Wo);
+      else
+        hipLaunchKernelGGL(dw5x5_s2_data_v8_k<uint64_t>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx,
+                           B, H, W, C, Ho, Wo);
+    }
+    MMRCA_CHECK_LAUNCH("dwconv5x5_bwd(data,v8)");
+  } else if (dx) {
+    const int64_t n = (int64_t)B * H * W * C;
+    MMRCA_DISPATCH_DTYPE(dtype, "dwconv5x5_bwd",
+      hipLaunchKernelGGL(dwconv5x5_bwd_data_k<T>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const T*)dy, (const T*)w, (T*)dx, B, H, W, C,
+                         Ho, Wo, stride);)
+    MMRCA_CHECK_LAUNCH("dwconv5x5_bwd(data)");
+  }
+  if (!dw) return 0;
+  const int n = C * 25;
+  const int64_t part_bytes = (int64_t)DW5_RED_CHUNKS * n * 4;
+  const bool ws_ok = ws && (((uintptr_t)ws) & 15) == 0;
+  if (dw_v8_ok(C, dtype, dy, x, dw)) {
+    const int64_t C8 = C / 8, ngrp = (int64_t)B * Ho * ((Wo + 3) / 4);
+    int64_t lanes = DW5_WG_THREADS / (5 * C8);
+    if (lanes > ngrp / DW5_WG_MIN_GROUPS) lanes = ngrp / DW5_WG_MIN_GROUPS;
+    if (lanes < 1) lanes = 1;
+    const bool use_ws = ws_ok && ws_bytes >= part_bytes + (int64_t)n * 4;
+    if (use_ws && lanes * n * 4 > ws_bytes - part_bytes) lanes = (ws_bytes - part_bytes) / ((int64_t)n * 4);
+    if (!use_ws && lanes > 64) lanes = 64;           // (fp32 atomics: 40 per thread)
+    const dim3 grid(blocks_for(lanes * 5 * C8, 256));
+    float* wsf = (float*)ws;
+#define DW5_WG(S_, WS_, I_) hipLaunchKernelGGL((dw5x5_wgrad_v8_k<S_, WS_, I_>), grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, dw, \
+                                                B, H, W, C, Ho, Wo, (unsigned)lanes, wsf)
+    if (use_ws) {
+      if (stride == 1) { if (s32) DW5_WG(1, true, unsigned); else DW5_WG(1, true, uint64_t); }
+      else { if (s32) DW5_WG(2, true, unsigned); else DW5_WG(2, true, uint64_t); }
+      dw5_reduce(wsf, (int)lanes, n, wsf + lanes * n, dw, st);
+    } else {
+      if (stride == 1) { if (s32) DW5_WG(1, false, unsigned); else DW5_WG(1, false, uint64_t); }
+      else { if (s32) DW5_WG(2, false, unsigned); else DW5_WG(2, false, uint64_t); }
+    }
+#undef DW5_WG
+    MMRCA_CHECK_LAUNCH("dwconv5x5_bwd(weight,v8)");
+    return 0;
+  }
+  // generic: ~2,048 blocks of 64 channels x a pixel range (at least 32 pixels), as many ranges as the workspace holds
+  const int64_t npix = (int64_t)B * Ho * Wo, cslices = (C + 63) / 64;
+  int64_t nblk = npix / 32 > 0 ? npix / 32 : 1;
+  if (nblk > 2048 / cslices) nblk = 2048 / cslices > 0 ? 2048 / cslices : 1;
+  const bool use_ws = ws_ok && ws_bytes >= part_bytes + (int64_t)n * 4;
+  if (use_ws && nblk * n * 4 > ws_bytes - part_bytes) nblk = (ws_bytes - part_bytes) / ((int64_t)n * 4);
+  const int64_t per = (npix + nblk - 1) / nblk;
+  nblk = (npix + per - 1) / per;
+  const dim3 grid((unsigned)cslices, (unsigned)nblk);
+  float* wsf = (float*)ws;
+  if (use_ws) {
+    MMRCA_DISPATCH_DTYPE(dtype, "dwconv5x5_bwd",
+      hipLaunchKernelGGL((dwconv5x5_bwd_weight_k<T, true>), grid, dim3(256), 0, st, (const T*)dy, (const T*)x, dw, B, H, W, C, Ho, Wo, stride, per, wsf);)
+    dw5_reduce(wsf, (int)nblk, n, wsf + nblk * n, dw, st);
+  } else {
+    MMRCA_DISPATCH_DTYPE(dtype, "dwconv5x5_bwd",
+      hipLaunchKernelGGL((dwconv5x5_bwd_weight_k<T, false>), grid, dim3(256), 0, st, (const T*)dy, (const T*)x, dw, B, H, W, C, Ho, Wo, stride, per, wsf);)
+  }
+  MMRCA_CHECK_LAUNCH("dwconv5x5_bwd(weight)");
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // BatchNorm2d over rows (torch.nn.BatchNorm2d as built by torchvision: eps 1e-3 EfficientNetV2 / 1e-5 ShuffleNetV2, momentum
 // 0.1).  Training: batch mean and BIASED variance normalise; running_var is updated with the UNBIASED variance.
 // Column reductions: block = 64 channels x 4 row lanes over a slice of rows -> LDS -> one atomic per channel per block.
@@ -1310,10 +1816,12 @@ col_moment2_flat_k(const bf16_t* __restrict__ x, float* __restrict__ ws, int64_t
   o[0] = make_float4(a0[0], a0[1], a0[2], a0[3]); o[1] = make_float4(a0[4], a0[5], a0[6], a0[7]);
   o[2] = make_float4(a1[0], a1[1], a1[2], a1[3]); o[3] = make_float4(a1[4], a1[5], a1[6], a1[7]);
 }
+template <int ACT>
 __global__ void __launch_bounds__(256)
 bn_act_bwd_reduce_flat_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const float* __restrict__ mean,
                          const float* __restrict__ rstd, const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta,
                          float* __restrict__ ws, int64_t rows, int C8, int act, int64_t T) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
   const int c0 = (int)(t % C8) * 8;
@@ -1435,10 +1943,12 @@ __global__ void bn_finish_shifted_k(const bf16_t* __restrict__ x, float* __restr
   }
 }
 
+template <int ACT>
 __global__ void __launch_bounds__(256)
 bn_act_bwd_reduce_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const float* __restrict__ mean,
                        const float* __restrict__ rstd, const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta,
                        float* __restrict__ sum_du, float* __restrict__ sum_duxh, int64_t rows, int C, int act, int64_t rows_per_block) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   __shared__ float red[4][8][17];
   const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
   const int c0 = blockIdx.x * 64 + cg * 8;
@@ -1578,9 +2088,10 @@ extern "C" int mmrca_bn_stats_ws(const void* x, float* mean, float* rstd, float*
   return bn_stats_impl(x, mean, rstd, running_mean, running_var, rows, C, ld, eps, momentum, train, dtype, ws, ws_bytes, flags, stream);
 }
 
-template <typename T>
+template <typename T, int ACT>
 __global__ void bn_act_fwd_k(const T* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                              const T* __restrict__ gamma, const T* __restrict__ beta, T* __restrict__ y, int64_t n, int C, int act) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
   const int c = (int)(idx % C);
@@ -1600,9 +2111,11 @@ __device__ __forceinline__ void bn_load8(const float* __restrict__ p, float (&v)
 // once per 16-byte vector -- with one vector per thread they were 3-5x the data loads and held the kernels at 4.2-4.7 TB/s --
 // and the BN_R data loads are issued together.
 #define BN_R 4
+template <int ACT>
 __global__ void __launch_bounds__(256)
 bn_act_fwd_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd, const bf16_t* __restrict__ gamma,
                 const bf16_t* __restrict__ beta, bf16_t* __restrict__ y, int64_t rows, int C8, int act) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t r0 = t / C8 * BN_R;
   if (r0 >= rows) return;
@@ -1625,10 +2138,12 @@ bn_act_fwd_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ mean, co
 }
 // the same followed by the block's residual connection: out = res + rowscale[sample] * act(bn(x))  (rowscale NULL = 1): the last
 // unit of an MBConv / FusedMBConv block writes the block output directly -- no y tensor, no separate residual_add pass
+template <int ACT>
 __global__ void __launch_bounds__(256)
 bn_act_fwd_res_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd, const bf16_t* __restrict__ gamma,
                     const bf16_t* __restrict__ beta, const bf16_t* __restrict__ res, const float* __restrict__ rowscale, bf16_t* __restrict__ out,
                     int64_t rows, int C8, int act, int64_t rows_per_sample) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t r0 = t / C8 * BN_R;
   if (r0 >= rows) return;
@@ -1661,13 +2176,14 @@ bn_act_fwd_res_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ mean
 // operation for operation -- and the threads of the first row group also store them (the backward reads them) and update the running
 // statistics.  One launch less per BatchNorm layer and step (146 of the ~2,000 launches of an EfficientNetV2-M step).  RES: the block's
 // residual connection as in bn_act_fwd_res_v8_k.
-template <bool RES>
+template <bool RES, int ACT>
 __global__ void __launch_bounds__(256)
 bn_act_fwd_fin_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ s1, const float* __restrict__ s2, const float* __restrict__ shift,
                     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, const bf16_t* __restrict__ res,
                     const float* __restrict__ rowscale, bf16_t* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out,
                     float* __restrict__ running_mean, float* __restrict__ running_var, int64_t rows, int C8, int act, int64_t rows_per_sample,
                     float n, float eps, float momentum) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t r0 = t / C8 * BN_R;
   if (r0 >= rows) return;
@@ -1720,11 +2236,13 @@ bn_act_fwd_fin_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ s1, 
     *reinterpret_cast<bn_b8*>(y + i0 + k * rs8) = o;
   }
 }
+template <int ACT>
 __global__ void __launch_bounds__(256)
 bn_act_bwd_apply_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
                       const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, const float* __restrict__ sum_du,
                       const float* __restrict__ sum_duxh, bf16_t* __restrict__ dx, int64_t rows, int C8, int act, float inv_rows, int train,
                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   if (dgamma && blockIdx.x == 0)
     for (int c = threadIdx.x; c < C8 * 8; c += blockDim.x) { dgamma[c] += sum_duxh[c]; dbeta[c] += sum_du[c]; }
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1763,17 +2281,17 @@ static bool bn_v8_ok(int C, int dtype, const void* a, const void* b, const void*
 
 extern "C" int mmrca_bn_act_fwd(const void* x, const float* mean, const float* rstd, const void* gamma, const void* beta, void* y,
                                 int64_t rows, int C, int act, int dtype, void* stream) {
-  MMRCA_REQUIRE(x && mean && rstd && gamma && beta && y && rows > 0 && C > 0 && act >= 0 && act <= 3, "bn_act_fwd: bad arguments");
+  MMRCA_REQUIRE(x && mean && rstd && gamma && beta && y && rows > 0 && C > 0 && act >= 0 && act <= 5, "bn_act_fwd: bad arguments");
   const int64_t n = rows * C;
   if (bn_v8_ok(C, dtype, x, y, gamma, beta) && ((((uintptr_t)mean) | ((uintptr_t)rstd)) & 15) == 0) {
-    hipLaunchKernelGGL(bn_act_fwd_v8_k, dim3(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, rows, C / 8, act);
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL(bn_act_fwd_v8_k<ACT>, dim3(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, rows, C / 8, act);)
     MMRCA_CHECK_LAUNCH("bn_act_fwd(v8)");
     return 0;
   }
   MMRCA_DISPATCH_DTYPE(dtype, "bn_act_fwd",
-    hipLaunchKernelGGL(bn_act_fwd_k<T>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, mean, rstd, (const T*)gamma,
-                       (const T*)beta, (T*)y, n, C, act);)
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bn_act_fwd_k<T, ACT>), dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, mean, rstd,
+                       (const T*)gamma, (const T*)beta, (T*)y, n, C, act);))
   MMRCA_CHECK_LAUNCH("bn_act_fwd");
   return 0;
 }
@@ -1783,13 +2301,13 @@ extern "C" int mmrca_bn_act_fwd(const void* x, const float* mean, const float* r
 extern "C" int mmrca_bn_act_fwd_res(const void* x, const float* mean, const float* rstd, const void* gamma, const void* beta, const void* res,
                                     const float* rowscale, void* out, int64_t rows, int C, int act, int64_t rows_per_sample, int dtype,
                                     void* stream) {
-  MMRCA_REQUIRE(x && mean && rstd && gamma && beta && res && out && rows > 0 && C > 0 && act >= 0 && act <= 3 && rows_per_sample > 0,
+  MMRCA_REQUIRE(x && mean && rstd && gamma && beta && res && out && rows > 0 && C > 0 && act >= 0 && act <= 5 && rows_per_sample > 0,
                 "bn_act_fwd_res: bad arguments");
   if (!(bn_v8_ok(C, dtype, x, out, gamma, beta) && ((((uintptr_t)mean) | ((uintptr_t)rstd) | ((uintptr_t)res)) & 15) == 0))
     return mmrca_fail(-3, "bn_act_fwd_res: only the bf16 / C %% 8 == 0 / 16-byte aligned case is built");
-    hipLaunchKernelGGL(bn_act_fwd_res_v8_k, dim3(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, (const bf16_t*)res, rowscale, (bf16_t*)out, rows,
-                     C / 8, act, rows_per_sample);
+  CONV_ACT_SWITCH(act, hipLaunchKernelGGL(bn_act_fwd_res_v8_k<ACT>, dim3(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256)), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, (const bf16_t*)res, rowscale,
+                     (bf16_t*)out, rows, C / 8, act, rows_per_sample);)
   MMRCA_CHECK_LAUNCH("bn_act_fwd_res");
   return 0;
 }
@@ -1815,30 +2333,31 @@ extern "C" int mmrca_bn_act_fwd_fin(const void* x, const float* s1, const float*
                                     const void* res, const float* rowscale, void* y, float* mean_out, float* rstd_out, float* running_mean,
                                     float* running_var, int64_t rows, int C, int act, int64_t rows_per_sample, float eps, float momentum,
                                     int dtype, void* stream) {
-  MMRCA_REQUIRE(x && s1 && s2 && shift && gamma && beta && y && mean_out && rstd_out && rows > 0 && C > 0 && act >= 0 && act <= 3 &&
+  MMRCA_REQUIRE(x && s1 && s2 && shift && gamma && beta && y && mean_out && rstd_out && rows > 0 && C > 0 && act >= 0 && act <= 5 &&
                 rows_per_sample > 0 && mean_out != s1 && mean_out != s2 && rstd_out != s1 && rstd_out != s2, "bn_act_fwd_fin: bad arguments");
   if (!(bn_v8_ok(C, dtype, x, y, gamma, beta) &&
         ((((uintptr_t)s1) | ((uintptr_t)s2) | ((uintptr_t)shift) | ((uintptr_t)res)) & 15) == 0))
     return mmrca_fail(-3, "bn_act_fwd_fin: only the bf16 / C %% 8 == 0 / 16-byte aligned case is built");
   const dim3 grid(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256));
   if (res)
-    hipLaunchKernelGGL(bn_act_fwd_fin_v8_k<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, s1, s2, shift, (const bf16_t*)gamma,
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bn_act_fwd_fin_v8_k<true, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, s1, s2, shift, (const bf16_t*)gamma,
                        (const bf16_t*)beta, (const bf16_t*)res, rowscale, (bf16_t*)y, mean_out, rstd_out, running_mean, running_var, rows, C / 8,
-                       act, rows_per_sample, (float)rows, eps, momentum);
+                       act, rows_per_sample, (float)rows, eps, momentum);)
   else
-    hipLaunchKernelGGL(bn_act_fwd_fin_v8_k<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, s1, s2, shift, (const bf16_t*)gamma,
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bn_act_fwd_fin_v8_k<false, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, s1, s2, shift, (const bf16_t*)gamma,
                        (const bf16_t*)beta, (const bf16_t*)nullptr, (const float*)nullptr, (bf16_t*)y, mean_out, rstd_out, running_mean,
-                       running_var, rows, C / 8, act, rows_per_sample, (float)rows, eps, momentum);
+                       running_var, rows, C / 8, act, rows_per_sample, (float)rows, eps, momentum);)
   MMRCA_CHECK_LAUNCH("bn_act_fwd_fin");
   return 0;
 }
 
 // backward, pass 1: du = dy * act'(u); sums[0][c] += du, sums[1][c] += du * xhat
-template <typename T>
+template <typename T, int ACT>
 __global__ void bn_act_bwd_reduce_k(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ mean,
                                     const float* __restrict__ rstd, const T* __restrict__ gamma, const T* __restrict__ beta,
                                     float* __restrict__ sum_du, float* __restrict__ sum_duxh, int64_t rows, int C, int act,
                                     int64_t rows_per_block) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   __shared__ float red[2][4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cl;
@@ -1861,11 +2380,12 @@ __global__ void bn_act_bwd_reduce_k(const T* __restrict__ dy, const T* __restric
   }
 }
 // pass 2: dx = gamma * rstd * (du - [train] (sum_du + xhat * sum_duxh) / n)
-template <typename T>
+template <typename T, int ACT>
 __global__ void bn_act_bwd_apply_k(const T* __restrict__ dy, const T* __restrict__ x, const float* __restrict__ mean,
                                    const float* __restrict__ rstd, const T* __restrict__ gamma, const T* __restrict__ beta,
                                    const float* __restrict__ sum_du, const float* __restrict__ sum_duxh, T* __restrict__ dx, int64_t n,
                                    int C, int act, float inv_rows, int train, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   // (the parameter gradients ride on block 0: the sums are complete before this launch starts -- it was a launch of its own)
   if (dgamma && blockIdx.x == 0)
     for (int c = threadIdx.x; c < C; c += blockDim.x) { dgamma[c] += sum_duxh[c]; dbeta[c] += sum_du[c]; }
@@ -1889,7 +2409,7 @@ __global__ void bn_param_grads_k(const float* __restrict__ sum_du, const float* 
 static int bn_act_bwd_impl(const void* dy, const void* x, const float* mean, const float* rstd, const void* gamma, const void* beta,
                            void* dx, float* dgamma, float* dbeta, float* scratch, int64_t rows, int C, int act, int train, int dtype,
                            void* stream, bool sums_ready, void* ws = nullptr, int64_t ws_bytes = 0, int flags = 0) {
-  MMRCA_REQUIRE(dy && x && mean && rstd && gamma && beta && scratch && rows > 0 && C > 0 && act >= 0 && act <= 3, "bn_act_bwd: bad arguments");
+  MMRCA_REQUIRE(dy && x && mean && rstd && gamma && beta && scratch && rows > 0 && C > 0 && act >= 0 && act <= 5, "bn_act_bwd: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   dim3 grid; int64_t per;
   col_grid(rows, C, &grid, &per);
@@ -1899,23 +2419,23 @@ static int bn_act_bwd_impl(const void* dy, const void* x, const float* mean, con
     const int64_t Tf = sums_ready ? 0 : bn_flat_threads(rows, C, C, dtype, dy, x, ws, ws_bytes);
     if (sums_ready) {}
     else if (Tf) {
-      hipLaunchKernelGGL(bn_act_bwd_reduce_flat_k, dim3(blocks_for(Tf, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, mean, rstd,
-                         (const bf16_t*)gamma, (const bf16_t*)beta, (float*)ws, rows, C / 8, act, Tf);
+      CONV_ACT_SWITCH(act, hipLaunchKernelGGL(bn_act_bwd_reduce_flat_k<ACT>, dim3(blocks_for(Tf, 256)), dim3(256), 0, st, (const bf16_t*)dy,
+                         (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, (float*)ws, rows, C / 8, act, Tf);)
       bn_flat_reduce((const float*)ws, Tf, C / 8, scratch, scratch + C, st);
     }
     else if (sizeof(T) == 2 && C % 8 == 0 && ((((uintptr_t)dy) | ((uintptr_t)x)) & 15) == 0)
-      hipLaunchKernelGGL(bn_act_bwd_reduce_v8_k, grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma,
-                         (const bf16_t*)beta, scratch, scratch + C, rows, C, act, per);
+      CONV_ACT_SWITCH(act, hipLaunchKernelGGL(bn_act_bwd_reduce_v8_k<ACT>, grid, dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)x, mean, rstd,
+                         (const bf16_t*)gamma, (const bf16_t*)beta, scratch, scratch + C, rows, C, act, per);)
     else
-    hipLaunchKernelGGL(bn_act_bwd_reduce_k<T>, grid, dim3(256), 0, st, (const T*)dy, (const T*)x, mean, rstd, (const T*)gamma, (const T*)beta,
-                       scratch, scratch + C, rows, C, act, per);
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bn_act_bwd_reduce_k<T, ACT>), grid, dim3(256), 0, st, (const T*)dy, (const T*)x, mean, rstd, (const T*)gamma,
+                       (const T*)beta, scratch, scratch + C, rows, C, act, per);)
     const bool v8 = dx && bn_v8_ok(C, dtype, dy, x, dx, gamma) && ((((uintptr_t)mean) | ((uintptr_t)rstd) | ((uintptr_t)scratch) | ((uintptr_t)beta)) & 15) == 0;
-    if (v8) hipLaunchKernelGGL(bn_act_bwd_apply_v8_k, dim3(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256)), dim3(256), 0, st, (const bf16_t*)dy,
+    if (v8) CONV_ACT_SWITCH(act, hipLaunchKernelGGL(bn_act_bwd_apply_v8_k<ACT>, dim3(blocks_for((rows + BN_R - 1) / BN_R * (C / 8), 256)), dim3(256), 0, st, (const bf16_t*)dy,
                                (const bf16_t*)x, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, (const float*)scratch,
-                               (const float*)(scratch + C), (bf16_t*)dx, rows, C / 8, act, 1.0f / (float)rows, train, dgamma && dbeta ? dgamma : nullptr, dbeta);
-    else if (dx) hipLaunchKernelGGL(bn_act_bwd_apply_k<T>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const T*)dy, (const T*)x, mean, rstd,
+                               (const float*)(scratch + C), (bf16_t*)dx, rows, C / 8, act, 1.0f / (float)rows, train, dgamma && dbeta ? dgamma : nullptr, dbeta);)
+    else if (dx) CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bn_act_bwd_apply_k<T, ACT>), dim3(blocks_for(n, 256)), dim3(256), 0, st, (const T*)dy, (const T*)x, mean, rstd,
                                (const T*)gamma, (const T*)beta, (const float*)scratch, (const float*)(scratch + C), (T*)dx, n, C, act,
-                               1.0f / (float)rows, train, dgamma && dbeta ? dgamma : nullptr, dbeta);)
+                               1.0f / (float)rows, train, dgamma && dbeta ? dgamma : nullptr, dbeta);))
   if (dgamma && dbeta && !dx) hipLaunchKernelGGL(bn_param_grads_k, dim3((C + 255) / 256), dim3(256), 0, st, scratch, scratch + C, dgamma, dbeta, C);
   MMRCA_CHECK_LAUNCH("bn_act_bwd");
   return 0;
@@ -2167,11 +2687,12 @@ extern "C" int mmrca_se_scale_bwd(const void* dy, const void* x, const void* s, 
 // the depthwise BatchNorm + SiLU that feeds the block, so with BN the sums that BatchNorm backward needs -- sum du and
 // sum du * xhat, du = dx * act'(xhat gamma + beta) -- are accumulated here as well (z = that BatchNorm's input): its separate
 // reduce pass over dx and z disappears.  block = (sample, 64 channels), as se_scale_bwd_v8_k.
-template <bool BN>
+template <bool BN, int ACT>
 __global__ void __launch_bounds__(256)
 se_dx_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ s, const bf16_t* __restrict__ dpool, bf16_t* __restrict__ dx, int HW, int C,
            float inv_hw, const bf16_t* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ rstd,
            const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, int act, float* __restrict__ sum_du, float* __restrict__ sum_duxh) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   __shared__ float red[4][8][17];
   const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
   const int c0 = blockIdx.y * 64 + cg * 8, b = blockIdx.x;
@@ -2240,14 +2761,14 @@ se_dx_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ s, const bf
 extern "C" int mmrca_se_dx(const void* dy, const void* s, const void* dpool, void* dx, int B, int HW, int C, int dtype, const void* z,
                            const float* mean, const float* rstd, const void* gamma, const void* beta, int act, float* sums, void* stream) {
   MMRCA_REQUIRE(dy && s && dpool && dx && B > 0 && HW > 0 && C > 0, "se_dx: bad arguments");
-  MMRCA_REQUIRE(!z || (mean && rstd && gamma && beta && sums && act >= 0 && act <= 3), "se_dx: the BatchNorm sums need mean, rstd, gamma, beta, sums");
+  MMRCA_REQUIRE(!z || (mean && rstd && gamma && beta && sums && act >= 0 && act <= 5), "se_dx: the BatchNorm sums need mean, rstd, gamma, beta, sums");
   if (!(pool_v8_ok(C, dtype, dy, s, dpool, dx) && (!z || ((((uintptr_t)z) & 15) == 0))))
     return mmrca_fail(-3, "se_dx: only the bf16 / C %% 8 == 0 / 16-byte aligned case is built");
   const dim3 grid(B, (C + 63) / 64);
-  if (z) hipLaunchKernelGGL(se_dx_v8_k<true>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)s, (const bf16_t*)dpool,
+  if (z) CONV_ACT_SWITCH(act, hipLaunchKernelGGL((se_dx_v8_k<true, ACT>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)s, (const bf16_t*)dpool,
                             (bf16_t*)dx, HW, C, 1.0f / (float)HW, (const bf16_t*)z, mean, rstd, (const bf16_t*)gamma, (const bf16_t*)beta, act,
-                            sums, sums + C);
-  else hipLaunchKernelGGL(se_dx_v8_k<false>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)s, (const bf16_t*)dpool,
+                            sums, sums + C);)
+  else hipLaunchKernelGGL((se_dx_v8_k<false, -1>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)s, (const bf16_t*)dpool,
                           (bf16_t*)dx, HW, C, 1.0f / (float)HW, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr,
                           (const bf16_t*)nullptr, (const bf16_t*)nullptr, 0, (float*)nullptr, (float*)nullptr);
   MMRCA_CHECK_LAUNCH("se_dx");
@@ -2255,8 +2776,9 @@ extern "C" int mmrca_se_dx(const void* dy, const void* s, const void* dpool, voi
 }
 
 // elementwise activation on [n] with an optional per-column bias (the 1x1 "convolutions" of squeeze-excitation carry a bias)
-template <typename T>
+template <typename T, int ACT>
 __global__ void bias_act_fwd_k(const T* __restrict__ x, const T* __restrict__ bias, T* __restrict__ y, int64_t n, int C, int act) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
   const float u = to_f(x[idx]) + (bias ? to_f(bias[idx % C]) : 0.f);
@@ -2264,17 +2786,19 @@ __global__ void bias_act_fwd_k(const T* __restrict__ x, const T* __restrict__ bi
 }
 /* y = act(x + bias[c]) on [rows, C]; x is the pre-activation WITHOUT bias (kept for the backward) */
 extern "C" int mmrca_bias_act_fwd(const void* x, const void* bias, void* y, int64_t rows, int C, int act, int dtype, void* stream) {
-  MMRCA_REQUIRE(x && y && rows > 0 && C > 0 && act >= 0 && act <= 3, "bias_act_fwd: bad arguments");
+  MMRCA_REQUIRE(x && y && rows > 0 && C > 0 && act >= 0 && act <= 5, "bias_act_fwd: bad arguments");
   const int64_t n = rows * C;
   MMRCA_DISPATCH_DTYPE(dtype, "bias_act_fwd",
-    hipLaunchKernelGGL(bias_act_fwd_k<T>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)bias, (T*)y, n, C, act);)
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bias_act_fwd_k<T, ACT>), dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x,
+                                            (const T*)bias, (T*)y, n, C, act);))
   MMRCA_CHECK_LAUNCH("bias_act_fwd");
   return 0;
 }
 // dx = dy * act'(x + bias);  dbias[c] += column sums of dx (tiny matrices: one thread per column)
-template <typename T>
+template <typename T, int ACT>
 __global__ void bias_act_bwd_k(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ bias, T* __restrict__ dx,
                                float* __restrict__ dbias, int64_t rows, int C, int act) {
+  if (ACT >= 0) act = ACT;              // (the launchers pass the code as ACT: straight-line activation code)
   // block = 64 columns x 4 row lanes (the [B, C] matrices of squeeze-excitation: one thread per column walking all B rows was
   // 60 us of dependent loads per call)
   // (round 3: 16 row lanes and four rows in flight per thread -- with 4 lanes a thread walked B / 4 = 32 rows one dependent pair of
@@ -2314,10 +2838,10 @@ __global__ void bias_act_bwd_k(const T* __restrict__ dy, const T* __restrict__ x
 }
 extern "C" int mmrca_bias_act_bwd(const void* dy, const void* x, const void* bias, void* dx, float* dbias, int64_t rows, int C, int act,
                                   int dtype, void* stream) {
-  MMRCA_REQUIRE(dy && x && dx && rows > 0 && C > 0 && act >= 0 && act <= 3, "bias_act_bwd: bad arguments");
+  MMRCA_REQUIRE(dy && x && dx && rows > 0 && C > 0 && act >= 0 && act <= 5, "bias_act_bwd: bad arguments");
   MMRCA_DISPATCH_DTYPE(dtype, "bias_act_bwd",
-    hipLaunchKernelGGL(bias_act_bwd_k<T>, dim3((C + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const T*)dy, (const T*)x, (const T*)bias,
-                       (T*)dx, dbias, rows, C, act);)
+    CONV_ACT_SWITCH(act, hipLaunchKernelGGL((bias_act_bwd_k<T, ACT>), dim3((C + 63) / 64), dim3(1024), 0, (hipStream_t)stream, (const T*)dy,
+                                            (const T*)x, (const T*)bias, (T*)dx, dbias, rows, C, act);))
   MMRCA_CHECK_LAUNCH("bias_act_bwd");
   return 0;
 }

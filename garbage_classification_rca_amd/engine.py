@@ -252,6 +252,11 @@ class MMRCAEngine:
         m = re.match(r"image_model\.(stem\.1|stage\d+|final_conv|conv5)\.", key)
         if m:
             return "image_stage_" + m.group(1)
+        # MobileNetV3-Large (classifier backbone): features.1 .. features.15 by output stride, features.16 + classifier.0 last
+        m = re.match(r"image_model\.(?:features\.(\d+)|classifier\.0)\.", key)
+        if m and m.group(1) != "0":
+            from .conv_engine import mbv3_stage_of
+            return "image_stage_" + mbv3_stage_of(16 if m.group(1) is None else int(m.group(1)))
         if key.startswith("image_model."):
             return "image_emb"
         return "head"
@@ -373,6 +378,8 @@ class MMRCAEngine:
                     if v.dim() == 4:
                         fan_out = v.shape[0] * v.shape[2] * v.shape[3]
                         v.copy_(torch.randn(v.shape, generator=g) * math.sqrt(2.0 / fan_out))
+                    elif v.dim() == 2:          # (MobileNetV3's classifier.0: torchvision's Linear init N(0, 0.01))
+                        v.copy_(torch.randn(v.shape, generator=g) * 0.01)
                     elif leaf == "weight":
                         v.fill_(1.0)
                     else:

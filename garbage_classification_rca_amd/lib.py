@@ -67,6 +67,8 @@ _SIGS = {
     "mmrca_dwconv3x3_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mmrca_dwconv3x3_bwd_ws": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "mmrca_dwconv3x3_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "mmrca_dwconv5x5_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "mmrca_dwconv5x5_bwd_ws": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "mmrca_conv3x3_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "mmrca_conv_bn_finish": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp],
     "mmrca_conv3x3_wgrad": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
@@ -631,7 +633,7 @@ def cast_f32_to_bf16(src, dst, n):
 # ---------------------------------------------------------------------------------------------------------
 # conv-backbone kernels (csrc/conv.hip); thin wrappers, raw pointers in
 # ---------------------------------------------------------------------------------------------------------
-CONV_NONE, CONV_SILU, CONV_RELU, CONV_SIGMOID = 0, 1, 2, 3
+CONV_NONE, CONV_SILU, CONV_RELU, CONV_SIGMOID, CONV_HSWISH, CONV_HSIGMOID = 0, 1, 2, 3, 4, 5
 
 
 def _out_hw(H, W, s):
@@ -648,6 +650,11 @@ def _dw_bwd_bytes(a):         # (dy, x, w, dx, dw, B, H, W, C, stride, dtype, ..
     return a[5] * a[8] * (Ho * Wo + 2 * a[6] * a[7]) * _esz(a[10])
 
 
+def _dw5_bwd_bytes(a):        # (dy, x, w, dx, dw, ...): dy once, plus x for the weight gradient, plus dx written
+    Ho, Wo = _out_hw(a[6], a[7], a[9])
+    return a[5] * a[8] * (Ho * Wo + (a[6] * a[7] if a[4] else 0) + (a[6] * a[7] if a[3] else 0)) * _esz(a[10])
+
+
 # ALGORITHMIC HBM bytes of one launch (every operand the op must read once + every result it must write once, per-channel
 # vectors ignored), from the launch arguments: the byte roofline of the conv step in bench.py
 _CONV_BYTES = {
@@ -656,6 +663,8 @@ _CONV_BYTES = {
     "mmrca_im2row3x3_tap": ("patches", _patch_bytes), "mmrca_col2im3x3_tap": ("patches", _patch_bytes),
     "mmrca_dwconv3x3_fwd": ("depthwise", lambda a: a[3] * a[6] * (a[4] * a[5] + _out_hw(a[4], a[5], a[7])[0] * _out_hw(a[4], a[5], a[7])[1]) * _esz(a[8])),
     "mmrca_dwconv3x3_bwd": ("depthwise", _dw_bwd_bytes), "mmrca_dwconv3x3_bwd_ws": ("depthwise", _dw_bwd_bytes),
+    "mmrca_dwconv5x5_fwd": ("depthwise 5x5", lambda a: a[3] * a[6] * (a[4] * a[5] + _out_hw(a[4], a[5], a[7])[0] * _out_hw(a[4], a[5], a[7])[1]) * _esz(a[8])),
+    "mmrca_dwconv5x5_bwd_ws": ("depthwise 5x5", lambda a: _dw5_bwd_bytes(a)),
     "mmrca_conv3x3_fwd": ("conv3x3 implicit GEMM", lambda a: (a[6] * a[7] * a[8] * (a[9] + a[10]) + 9 * a[9] * a[10]) * _esz(a[11])),
     "mmrca_conv3x3_wgrad": ("conv3x3 implicit GEMM", lambda a: a[3] * a[4] * a[5] * (a[6] + a[7]) * _esz(a[8]) + 9 * a[6] * a[7] * 4),
     "mmrca_gemm_bnstats": ("GEMM (1x1 / patch)", lambda a: (a[3] * a[5] + a[4] * a[5] + a[3] * a[4]) * _esz(a[9])),
@@ -733,6 +742,17 @@ def dwconv3x3_bwd(dy, x, w, dx, dw, B, H, W, C, stride, dtype, ws=None):
         _c("mmrca_dwconv3x3_bwd", ptr(dy), ptr(x), ptr(w), ptr(dx), ptr(dw), B, H, W, C, stride, dtype)
     else:
         _c("mmrca_dwconv3x3_bwd_ws", ptr(dy), ptr(x), ptr(w), ptr(dx), ptr(dw), B, H, W, C, stride, dtype, ptr(ws), ws.numel() * ws.element_size())
+
+
+def dwconv5x5_fwd(x, w, y, B, H, W, C, stride, dtype):
+    _dev(x, "dwconv5x5 x")
+    _c("mmrca_dwconv5x5_fwd", ptr(x), ptr(w), ptr(y), B, H, W, C, stride, dtype)
+
+
+def dwconv5x5_bwd(dy, x, w, dx, dw, B, H, W, C, stride, dtype, ws=None):
+    """dx / dw may be None; ws: optional scratch for the weight gradient's partial sums (fixed-order reduction instead of atomics)"""
+    _c("mmrca_dwconv5x5_bwd_ws", ptr(dy), ptr(x), ptr(w), ptr(dx), ptr(dw), B, H, W, C, stride, dtype, ptr(ws),
+       0 if ws is None else ws.numel() * ws.element_size())
 
 
 def conv3x3_stat_slots(B, H, W) -> int:

@@ -190,7 +190,7 @@ int mmrca_gelu_bwd_colsum(const void* dG, const void* H, void* dH, float* db, in
  * CVPR_code/multimodal_model.py:11-36, 113-126 and shufflenet_v2_x2_0 (models.py:261-278), on NHWC activations stored as
  * row-major [B*H*W, C] matrices.  1x1 convolutions are mmrca_gemm on those rows; a full 3x3 convolution is
  * mmrca_im2row3x3 + mmrca_gemm (patch row = col[c*9 + ky*3 + kx], the flattening of torchvision's [Cout, Cin, 3, 3] weight).
- * CONV activations: 0 none, 1 SiLU, 2 ReLU, 3 sigmoid. ------------------------------------------------------------- */
+ * CONV activations: 0 none, 1 SiLU, 2 ReLU, 3 sigmoid, 4 hard-swish, 5 hard-sigmoid. ------------------------------------------------------------- */
 /* images [B, C, H, W] fp32 (the tensor main_both.py:100-103 moves to the device) -> rows [B*H*W, C] in `dtype` */
 int mmrca_nchw_to_rows(const float* images, void* x, int B, int C, int H, int W, int dtype, void* stream);
 /* 3x3 patches, padding 1, stride 1 | 2: col[B*Ho*Wo, ldk] (ldk >= 9C), and the gather that sums a patch gradient back */
@@ -228,6 +228,13 @@ int mmrca_dwconv3x3_bwd(const void* dy, const void* x, const void* w, void* dx, 
  * stride-1 bf16 weight gradient then writes per-block partial sums there and adds them up in a second kernel instead of issuing
  * device-scope fp32 atomics */
 int mmrca_dwconv3x3_bwd_ws(const void* dy, const void* x, const void* w, void* dx, float* dw, int B, int H, int W, int C, int stride,
+                           int dtype, void* ws, int64_t ws_bytes, void* stream);
+/* depthwise 5x5 (torch Conv2d(C, C, 5, stride, 2, groups=C, bias=False): MobileNetV3-Large); w [C, 25] in `dtype`; dw fp32 [C, 25] +=;
+ * dx / dw / ws may be NULL.  With a workspace (16-byte aligned, at least 17 * C * 100 bytes; 44 MiB gives every shape its full number
+ * of pixel lanes) the weight gradient's partial sums go there and are added in a fixed order: bitwise reproducible, no atomics.  A
+ * smaller or missing workspace: fp32 atomics */
+int mmrca_dwconv5x5_fwd(const void* x, const void* w, void* y, int B, int H, int W, int C, int stride, int dtype, void* stream);
+int mmrca_dwconv5x5_bwd_ws(const void* dy, const void* x, const void* w, void* dx, float* dw, int B, int H, int W, int C, int stride,
                            int dtype, void* ws, int64_t ws_bytes, void* stream);
 /* torch.nn.BatchNorm2d over the rows of x [rows, C] (ld): train != 0 -> batch mean / biased variance into mean, rstd and, with
  * momentum > 0, the running statistics update (unbiased variance); train == 0 -> mean / rstd from the running statistics */

@@ -5,7 +5,7 @@ parameter trainable: forward, cross entropy, backward, SGD step, gradient zeroin
     python tools/classifier_bench.py [--steps 10] [--warmup 3] [--only vit_b16_bf16,...]
 
 Configurations: ViT-B/16 image-only at B = 128 in bf16 and bf16x3f, DistilBERT text-only at B = 128 (captions of 64 tokens, as bench.py),
-EfficientNetV2-M at 480 x 480, B = 64 (bf16x3f), and, for comparison, the MM_RCA ViT-B/16 + DistilBERT step at B = 128 in bf16.
+EfficientNetV2-M at 480 x 480, B = 64 (bf16x3f), MobileNetV3-Large at 320 x 320, B = 256 (bf16 and bf16x3f), and, for comparison, the MM_RCA ViT-B/16 + DistilBERT step at B = 128 in bf16.
 One JSON line per configuration.
 """
 import argparse
@@ -28,6 +28,8 @@ CONFIGS = {
     "vit_b16_bf16x3f": ("image", "transformer_B16", "bf16x3f", 128),
     "distilbert_bf16x3f": ("text", "distilbert", "bf16x3f", 128),
     "effv2m_480_bf16x3f": ("image", "eff_v2_medium", "bf16x3f", 64),
+    "mb_320_bf16": ("image", "mb", "bf16", 256),
+    "mb_320_bf16x3f": ("image", "mb", "bf16x3f", 256),
     "mm_rca_vit_b16_distilbert_bf16": ("both", "transformer_B16", "bf16", 128),
 }
 
