@@ -21,7 +21,7 @@ import torch
 from .CustomImageTextFolder import CustomImageTextFolder
 from .main_both import DecodeOnly, Transforms, collate_decoded
 from .training import stage_images, trim_caption_columns
-from .multimodal_model import MM_RCA
+from .multimodal_model import MM_RCA, Hierarchical
 from .options import args_parser
 from .training import mode_config_dict
 
@@ -109,16 +109,20 @@ def main(argv=None):
     torch.manual_seed(42)
     np.random.seed(42)
     _batch_size = 16
-    if args.late_fusion != "MM_RCA":
+    if args.late_fusion not in ("MM_RCA", "hierarchical"):
         print("Wrong late fusion strategy: ", args.late_fusion)
         sys.exit(1)
     from .conv_engine import CONV_MODELS
     from . import spec as S
     image_model = args.image_model if (args.image_model in S.VISION_SPECS or args.image_model in CONV_MODELS) else "EffNetv2-Medium"
-    model = MM_RCA(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout, args.num_neurons_FC,
-                   args.text_model, _batch_size, args.reverse, args.features_only, args.cross_attention_only,
-                   image_model_name=image_model, dtype={"bf16": torch.bfloat16, "fp32": torch.float32}.get(args.dtype, args.dtype), device=device,
-                   image_size=args.image_size)
+    build_kw = dict(image_model_name=image_model, dtype={"bf16": torch.bfloat16, "fp32": torch.float32}.get(args.dtype, args.dtype), device=device,
+                    image_size=args.image_size)
+    if args.late_fusion == "hierarchical":
+        model = Hierarchical(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout, args.num_neurons_FC,
+                             args.text_model, _batch_size, args.reverse, **build_kw)
+    else:
+        model = MM_RCA(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout, args.num_neurons_FC,
+                       args.text_model, _batch_size, args.reverse, args.features_only, args.cross_attention_only, **build_kw)
     model.load_state_dict(torch.load(args.model_path, map_location=device))
     model.eval()
     WIDTH, HEIGHT = model.get_image_size()

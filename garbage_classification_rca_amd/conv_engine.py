@@ -722,8 +722,11 @@ class ConvEncoder:
         return dx, bnargs is not None
 
     # ------------------------------------------------------------------ whole network
-    def forward(self, images, save: bool, train: bool, seed: int = 0):
-        """images [B,3,H,W] fp32 in HBM -> features [B, dim] (the pooled vector MM_RCA consumes, multimodal_model.py:659)."""
+    def forward(self, images, save: bool, train: bool, seed: int = 0, taps=None):
+        """images [B,3,H,W] fp32 in HBM -> features [B, dim] (the pooled vector MM_RCA consumes, multimodal_model.py:659).
+        taps (optional): {stage name: (k, out, ld)} -- behind the last block of that stage its output map is average-pooled with k x k
+        floor windows (mmrca_hier_pool_fwd) into the fp32 tensor `out` (row pitch ld, NCHW order), right where the activation is
+        produced, so that save=False keeps alternating its two buffer pools."""
         dt = self.cdt
         B, C, H, Wd = images.shape
         if C != 3:
@@ -736,7 +739,11 @@ class ConvEncoder:
         self._bn_bwd_seen.clear()
         x0 = self.buf("in.rows", B * H * Wd, 3)
         L.nchw_to_rows(images.to(torch.float32).contiguous(), x0, B, 3, H, Wd, dt)
-        saved = dict(B=B, blocks=[], train=train)
+        saved = dict(B=B, blocks=[], train=train, taps={})
+        if taps:
+            unknown = [n for n in taps if n not in {b["stage"] for b in self.blocks}]
+            if unknown:
+                raise L.MmrcaError(f"conv backbone {self.name}: no stage named {unknown}")
         x, h, w, saved["stem"] = self._unit_fwd(self.stem, x0, B, H, Wd, "stem", train, save)
         if self.name == "shuffle_net":
             Ho, Wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
@@ -817,6 +824,10 @@ class ConvEncoder:
                 bs["inplace"] = inplace
                 x = self._shuffle_cat(x, y2, rows, Cc, f"{tag}.out", first_is_full=True)
             saved["blocks"].append(bs)
+            if taps and blk["stage"] in taps and (bi + 1 == len(self.blocks) or self.blocks[bi + 1]["stage"] != blk["stage"]):
+                k, out, ld = taps[blk["stage"]]
+                L.hier_pool_fwd(x, out, ld, B, h, w, x.shape[1], k, dt)
+                saved["taps"][blk["stage"]] = (bi, h, w, x.shape[1], k)
         y, h, w, saved["final"] = self._unit_fwd(self.final, x, B, h, w, "final", train, save)
         saved["HW"] = h * w
         if self.tail is not None:
@@ -872,8 +883,10 @@ class ConvEncoder:
         L.channel_deinterleave2(dout, d1, bf, d2, rows, bf, self.cdt)
         return d1, d2
 
-    def backward(self, dfeat):
-        """dfeat [B, dim] -> accumulates every parameter gradient of the backbone (no gradient w.r.t. the images)."""
+    def backward(self, dfeat, dtaps=None):
+        """dfeat [B, dim] -> accumulates every parameter gradient of the backbone (no gradient w.r.t. the images).
+        dtaps (optional): {stage name: (d, ld)} for stages tapped in forward(): the fp32 gradient of the pooled vector, added
+        (mmrca_hier_pool_bwd) into the gradient at the stage's output before the stage's blocks run."""
         sv = self.saved
         if sv is None:
             raise L.MmrcaError("conv backbone: backward() needs forward(save=True)")
@@ -900,6 +913,10 @@ class ConvEncoder:
         ready("image_stage_" + ("conv5" if self.name == "shuffle_net" else "final_conv"))
         for bi in reversed(range(len(self.blocks))):
             blk, bs = self.blocks[bi], sv["blocks"][bi]
+            if dtaps and blk["stage"] in dtaps and sv["taps"].get(blk["stage"], (None,))[0] == bi:
+                _, th, tw, tc, tk = sv["taps"][blk["stage"]]
+                d, ld = dtaps[blk["stage"]]
+                L.hier_pool_bwd(d, ld, dx, B, th, tw, tc, tk, dt)
             gp = f"g{bi % 2}"          # gradient buffers alternate between two pools: the incoming gradient (written by block
                                        # bi + 1) must survive until this block's residual sum
             if blk["kind"] in ("fused", "mb"):

@@ -578,8 +578,15 @@ class MMRCAEngine:
         return (base * 1000003 + layer * 16 + site + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
     # ------------------------------------------------------------------ text encoder
-    def _text_forward(self, ids, mask, save, drop_p: float = 0.0, drop_seed: int = 0, pack: Optional[TextPack] = None):
+    def _text_forward(self, ids, mask, save, drop_p: float = 0.0, drop_seed: int = 0, pack: Optional[TextPack] = None, taps=None):
+        """taps (optional): HuggingFace ``hidden_states`` indices n in [1, layers - 1] (hidden_states[n] = the output of encoder layer
+        n - 1, which runs on all rows); the class-token rows [B, D] of each come back as ``saved["taps"][n]``."""
         s, P = self.ts, "text_model."
+        if taps:
+            bad = [n for n in taps if not 1 <= int(n) <= s.layers - 1]
+            if bad:
+                raise L.MmrcaError(f"text taps {bad}: hidden_states indices must lie in [1, {s.layers - 1}] for {s.name}")
+        tap_rows = {}
         B, T = ids.shape
         cap, D, Fd, H = B * T, s.dim, s.ffn, s.heads          # buffers are sized for the padded layout
         dh = D // H
@@ -640,7 +647,7 @@ class MMRCAEngine:
                                    ctx_c=ctx_c, tail=True))
                 cls = xn[:B].clone()
                 return cls, dict(B=B, T=T, M=M, cu=cu, first=first, ids32=ids32, pos=pos, mask32=mask32, emb=emb, mean0=mean0, rstd0=rstd0, layers=layers,
-                                 drop_p=dp, drop_seed=drop_seed)
+                                 drop_p=dp, drop_seed=drop_seed, taps=tap_rows)
             self._mha_fwd(qkv, mask32, ctx, lse, B, H, T, dh, drop_p=dp, drop_seed=sd(i, 1), cu=cu)
             att = fb("tmpD", D)
             self._lin_fwd(ctx, P + K["o"] + ".weight", P + K["o"] + ".bias", att, M, D, D)
@@ -656,11 +663,15 @@ class MMRCAEngine:
             self._ln_fwd(f, x1, P + K["ln2"], s2, xn, m2, r2, M, D, s.ln_eps, in_drop=(dp, sd(i, 3)), to_gemm=(i + 1 < s.layers))
             layers.append(dict(x=x, qkv=qkv, ctx=ctx, lse=lse, s1=s1, x1=x1, m1=m1, r1=r1, h=h, g=g, s2=s2, m2=m2, r2=r2))
             x = xn
+            if taps and (i + 1) in taps:
+                tap_rows[i + 1] = x.index_select(0, first)
         cls = x.index_select(0, first)
         return cls, dict(B=B, T=T, M=M, cu=cu, first=first, ids32=ids32, pos=pos, mask32=mask32, emb=emb, mean0=mean0, rstd0=rstd0, layers=layers,
-                         drop_p=dp, drop_seed=drop_seed)
+                         drop_p=dp, drop_seed=drop_seed, taps=tap_rows)
 
-    def _text_backward(self, dcls, sv):
+    def _text_backward(self, dcls, sv, dtaps=None):
+        """dtaps (optional): {hidden_states index n: gradient [B, D] at its class-token rows}, added into the residual-stream gradient
+        at the output of layer n - 1 before that layer's backward runs"""
         s, P = self.ts, "text_model."
         B, T = sv["B"], sv["T"]
         M, D, Fd, H = sv["M"], s.dim, s.ffn, s.heads
@@ -677,6 +688,8 @@ class MMRCAEngine:
                 self._text_backward_tail(dcls, sv, dx)
                 continue
             K, a = S.text_layer_keys(s, i), sv["layers"][i]
+            if dtaps and (i + 1) in dtaps:
+                dx.index_add_(0, first, dtaps[i + 1].to(dx.dtype))
             ds2 = gb("ds2", D)
             dp, sd = sv["drop_p"], (lambda layer, site: self._site_seed(sv["drop_seed"], layer, site))
             post_attn_drop = dp if s.name != "distilbert" else 0.0

@@ -135,9 +135,16 @@ _SIGS = {
     "mmrca_linear_cls_fwd": [_vp, _i32, _vp, _vp, _vp] + [_i32] * 3 + [_f32, _u64, _i32, _vp],
     "mmrca_linear_cls_bwd": [_vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 3 + [_f32, _u64, _i32, _vp],
     "mmrca_sd_rowscale": [_vp, _vp, _i32, _i32, _u64, _vp],
+    "mmrca_hier_pool_fwd": [_vp, _vp] + [_i32] * 7 + [_vp],
+    "mmrca_hier_pool_bwd": [_vp, _i32, _vp] + [_i32] * 6 + [_vp],
+    "mmrca_hier_norm_fwd": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _u64, _u64, _vp],
+    "mmrca_hier_norm_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _u64, _u64, _vp],
+    "mmrca_hier_linear_relu_fwd": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
+    "mmrca_hier_linear_relu_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["mmrca_last_error", "mmrca_version", "mmrca_debug_set", "mmrca_bn_flat_set", "mmrca_debug_attn_stamps", "mmrca_gemm_splitk_workspace_bytes", "mmrca_gemm_streamk_workspace_bytes",
-                                  "mmrca_head_bwd_workspace_bytes", "mmrca_conv3x3_stat_slots", "mmrca_gemm_bnstats_slots"])
+                                  "mmrca_head_bwd_workspace_bytes", "mmrca_conv3x3_stat_slots", "mmrca_gemm_bnstats_slots",
+                                  "mmrca_hier_linear_workspace_bytes"])
 
 
 def load(build_if_missing: bool = False):
@@ -159,6 +166,8 @@ def load(build_if_missing: bool = False):
     lib.mmrca_gemm_splitk_workspace_bytes.restype = _i64
     lib.mmrca_gemm_streamk_workspace_bytes.argtypes = []
     lib.mmrca_gemm_streamk_workspace_bytes.restype = _i64
+    lib.mmrca_hier_linear_workspace_bytes.argtypes = [_i32, _i32, _i32]
+    lib.mmrca_hier_linear_workspace_bytes.restype = _i64
     lib.mmrca_conv3x3_stat_slots.argtypes = [_i32, _i32, _i32]
     lib.mmrca_conv3x3_stat_slots.restype = _i64
     lib.mmrca_last_error.restype = C.c_char_p
@@ -592,6 +601,66 @@ def adamw_step(p, g, m, v, lp, n, lr, b1, b2, eps, wd, step, grad_scale=1.0, lp_
 
 
 SEED_EPOCH_STRIDE = 1000003      # = MMRCA_SEED_EPOCH_STRIDE (csrc/common.h) = the per-step stride of engine._site_seed
+# ---- head of the hierarchical late-fusion model (csrc/hier_head.hip) --------------------------------------------------------
+def _u64v(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def hier_pool_fwd(x, out, ld_out, B, H, W, Cc, k, dtype):
+    """AvgPool2d(k, k) (floor windows) of the NHWC rows x [B*H*W, C] -> fp32, NCHW order, at out[b*ld_out + ...] (out may be a column
+    window of a wider [B, ld_out] buffer)"""
+    _dev(x, "hier_pool x")
+    with _Bracket("hier_pool_fwd", (B, H, W, Cc, k)):
+        _check(load().mmrca_hier_pool_fwd(ptr(x), ptr(out), ld_out, B, H, W, Cc, k, dtype, stream_ptr()), "mmrca_hier_pool_fwd")
+
+
+def hier_pool_bwd(d, ld_d, dx, B, H, W, Cc, k, dtype):
+    """dx [B*H*W, C] += d / k^2 at the pixels the windows cover"""
+    _dev(dx, "hier_pool dx")
+    with _Bracket("hier_pool_bwd", (B, H, W, Cc, k)):
+        _check(load().mmrca_hier_pool_bwd(ptr(d), ld_d, ptr(dx), B, H, W, Cc, k, dtype, stream_ptr()), "mmrca_hier_pool_bwd")
+
+
+def _seg_array(seg_off):
+    return (C.c_int * len(seg_off))(*[int(v) for v in seg_off])
+
+
+def hier_norm_fwd(raw, x, inv, B, ld, seg_off, nseg_a, drop_p, seed_a, seed_b):
+    """per-segment L2 normalisation + dropout (group a = the first nseg_a segments, group b the rest; one mask seed each)"""
+    _dev(raw, "hier_norm raw")
+    with _Bracket("hier_norm_fwd", (B, ld)):
+        _check(load().mmrca_hier_norm_fwd(ptr(raw), ptr(x), ptr(inv), B, ld, _seg_array(seg_off), len(seg_off) - 1, nseg_a, float(drop_p),
+                                          _u64v(seed_a), _u64v(seed_b), stream_ptr()), "mmrca_hier_norm_fwd")
+
+
+def hier_norm_bwd(dx, raw, inv, draw, B, ld, seg_off, nseg_a, drop_p, seed_a, seed_b):
+    _dev(dx, "hier_norm dx")
+    with _Bracket("hier_norm_bwd", (B, ld)):
+        _check(load().mmrca_hier_norm_bwd(ptr(dx), ptr(raw), ptr(inv), ptr(draw), B, ld, _seg_array(seg_off), len(seg_off) - 1, nseg_a,
+                                          float(drop_p), _u64v(seed_a), _u64v(seed_b), stream_ptr()), "mmrca_hier_norm_bwd")
+
+
+def hier_linear_workspace_bytes(B, N, K) -> int:
+    return int(load().mmrca_hier_linear_workspace_bytes(B, N, K))
+
+
+def hier_linear_relu_fwd(X, ldx, W, b, Y, ldy, ws, B, N, K):
+    """Y = relu(X W^T + b) with the contraction split over the chip; ws: a uint8 / fp32 workspace of hier_linear_workspace_bytes"""
+    _dev(X, "hier_linear X")
+    with _Bracket("hier_linear_relu_fwd", (B, N, K)):
+        _check(load().mmrca_hier_linear_relu_fwd(ptr(X), ldx, ptr(W), ptr(b), ptr(Y), ldy, ptr(ws), ws.numel() * ws.element_size(), B, N, K,
+                                                 stream_ptr()), "mmrca_hier_linear_relu_fwd")
+
+
+def hier_linear_relu_bwd(dY, lddy, Y, ldy, X, ldx, W, dW, db, dX, lddx, ws, B, N, K):
+    """dW += dZ^T X, db += colsum(dZ), dX (or None) = dZ W with dZ = dY * (Y > 0); ws: as in the forward (None is fine without dX)"""
+    _dev(dY, "hier_linear dY")
+    with _Bracket("hier_linear_relu_bwd", (B, N, K)):
+        _check(load().mmrca_hier_linear_relu_bwd(ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, ptr(ws),
+                                                 0 if ws is None else ws.numel() * ws.element_size(), B, N, K, stream_ptr()),
+               "mmrca_hier_linear_relu_bwd")
+
+
 _seed_epoch = 0                  # host view of the device-side mask epoch (0 = eager launches draw the seeds they are given)
 
 

@@ -10,7 +10,7 @@ everything trainable for ``--ft_epochs`` at lr/``--fraction_lr``, main_both.py:5
 the fine-tuning phase only, best-validation checkpointing with the reference's file-name pattern, wandb keys (wandb is
 optional here: it needs network).  Replaced: ``nn.DataParallel`` -> sharded sampler + overlapped RCCL gradient
 all-reduce; ``torch.optim`` -> fused flat-arena optimizers (same update rules).
-Only ``--late_fusion=MM_RCA`` is constructible, as in the reference (SURVEY.md header).
+``--late_fusion=MM_RCA`` and ``--late_fusion=hierarchical`` are built (SURVEY.md header); every other value exits as in the reference.
 """
 from __future__ import annotations
 
@@ -25,7 +25,7 @@ import torch
 
 from . import distributed as D
 from .CustomImageTextFolder import CustomImageTextFolder, SyntheticImageTextDataset
-from .multimodal_model import MM_RCA
+from .multimodal_model import MM_RCA, Hierarchical
 from .optim import FlatAdamW, FlatSGD
 from .options import args_parser
 from .training import (calculate_set_accuracy, get_class_weights_from_counts, mode_config_dict, run_one_epoch)
@@ -155,13 +155,19 @@ def main(argv=None):
     print("Text Model: {}".format(args.text_model))
     print("Image Model: {}".format(args.image_model))
     _batch_size, _batch_size_FT = args.batch_size, args.batch_size_FT
-    if args.late_fusion != "MM_RCA":
+    build_kw = dict(image_model_name=args.image_model, dtype={"bf16": torch.bfloat16, "fp32": torch.float32}.get(args.dtype, args.dtype),
+                    device=device, image_size=args.image_size)
+    if args.late_fusion == "MM_RCA":
+        global_model = MM_RCA(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout,
+                              args.num_neurons_FC, args.text_model, _batch_size, args.reverse, args.features_only,
+                              args.cross_attention_only, **build_kw)
+    elif args.late_fusion == "hierarchical":
+        # the reference's eight positionals (main_both.py:319-327); a configuration the three linears do not fit raises here
+        global_model = Hierarchical(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout,
+                                    args.num_neurons_FC, args.text_model, _batch_size, args.reverse, **build_kw)
+    else:
         print("Wrong late fusion strategy: ", args.late_fusion)       # main_both.py:341-343
         sys.exit(1)
-    global_model = MM_RCA(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout,
-                          args.num_neurons_FC, args.text_model, _batch_size, args.reverse, args.features_only,
-                          args.cross_attention_only, image_model_name=args.image_model,
-                          dtype={"bf16": torch.bfloat16, "fp32": torch.float32}.get(args.dtype, args.dtype), device=device, image_size=args.image_size)
     print("Num total parameters of the model: {}".format(count_parameters(global_model)))
     wandb = _wandb() if is_main else _NoWandb()
     wandb.init(project="Garbage Classification Both - MI355X", config=dict(args.__dict__))

@@ -1,4 +1,4 @@
-"""Drop-in ``MM_RCA`` module (mirrors CVPR_code/multimodal_model.py:156-328, 636-728 of the reference).
+"""Drop-in ``MM_RCA`` and ``Hierarchical`` modules (mirrors CVPR_code/multimodal_model.py:156-328, 636-728 of the reference).
 
 Same constructor argument order as the reference's call at main_both.py:306-317, same
 ``forward(_input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False)``, same
@@ -127,7 +127,7 @@ class EffV2MediumAndDistilbertGated(torch.nn.Module):
         self.image_size = 224 if image_model_name in S.VISION_SPECS else int(image_size or (480 if image_model_name in ("eff_v2_medium", "EffNetv2-Medium") else 224))
         if isinstance(dtype, str) and dtype.lower() in ("bf16", "fp32", "f32"):
             dtype = torch.bfloat16 if dtype.lower() == "bf16" else torch.float32
-        self.engine = MMRCAEngine(text_model_name, image_model_name, n_classes, reverse, mode, dtype, device, image_size=self.image_size)
+        self.engine = self._make_engine(text_model_name, image_model_name, n_classes, reverse, mode, dtype, device)
         self.engine.init_parameters(init_seed)
         self.drop_ratio = float(drop_ratio)
         # train-mode dropout inside the HF text encoders (DistilBertConfig.dropout = attention_dropout = 0.1; torchvision's
@@ -165,14 +165,21 @@ class EffV2MediumAndDistilbertGated(torch.nn.Module):
         if build_unused_parameters:
             # present-but-unused keys of the reference constructor (:199-328): kept for checkpoint interchange
             g = torch.Generator().manual_seed(init_seed + 1)
-            for k, shp in S.head_unused_params(self.engine.d_img, self.engine.d_txt, n_classes, num_neurons_fc,
-                                               batch_size, self.features_only, self.cross_attention_only):
+            for k, shp in self._unused_param_entries(n_classes, num_neurons_fc, batch_size):
                 if k in self._arena_params:
                     continue
                 t = torch.randn(shp, generator=g) * 0.02 if len(shp) else torch.tensor(float(np.log(1 / 0.07)))
                 self._add_head_param(k, torch.nn.Parameter(t.to(device)))
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self.config_hidden_size = self.engine.d_txt
+
+    def _make_engine(self, text_model_name, image_model_name, n_classes, reverse, mode, dtype, device):
+        return MMRCAEngine(text_model_name, image_model_name, n_classes, reverse, mode, dtype, device, image_size=self.image_size)
+
+    def _unused_param_entries(self, n_classes, num_neurons_fc, batch_size):
+        """(key, shape) of the constructor's layers this model's forward does not touch (keys that live in the arena are skipped)"""
+        return S.head_unused_params(self.engine.d_img, self.engine.d_txt, n_classes, num_neurons_fc, batch_size, self.features_only,
+                                    self.cross_attention_only)
 
     def _add_head_param(self, dotted, p):
         node = self
@@ -275,13 +282,10 @@ class EffV2MediumAndDistilbertGated(torch.nn.Module):
         return self
 
     def forward(self, _input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False):
-        raise NotImplementedError("only the MM_RCA forward is built (other fusion forwards are unconstructible in the reference)")
+        raise NotImplementedError("only the MM_RCA and Hierarchical forwards are built (the other fusion forwards have no launcher in the reference)")
 
-
-class MM_RCA(EffV2MediumAndDistilbertGated):
-    """multimodal_model.py:636-728."""
-
-    def forward(self, _input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False):
+    def _engine_forward(self, _input_ids, _attention_mask, _images, eval, remove_image, remove_text):
+        """modality dropout on the host, then the whole model as one autograd node over the engine"""
         self._images, self._input_ids, self._attention_mask = _images, _input_ids, _attention_mask
         self.drop_modalities(eval, remove_image, remove_text)
         drop_p = self.drop_ratio if self.training else 0.0           # nn.Dropout(p=drop_ratio) at :719
@@ -292,3 +296,41 @@ class MM_RCA(EffV2MediumAndDistilbertGated):
                                        drop_p, self._drop_seed + self._fwd_count, bool(need_grad and (tt or ti)),
                                        self.enc_dropout if self.training else 0.0)
         return logits
+
+
+class MM_RCA(EffV2MediumAndDistilbertGated):
+    """multimodal_model.py:636-728."""
+
+    def forward(self, _input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False):
+        return self._engine_forward(_input_ids, _attention_mask, _images, eval, remove_image, remove_text)
+
+
+class Hierarchical(EffV2MediumAndDistilbertGated):
+    """multimodal_model.py:729-818: multi-level features of both backbones (EfficientNetV2-M stage3 / stage6 / pooled; the class
+    token of the last hidden state and of hidden_states[2] / [4]), each L2-normalised, concatenated, dropped, and classified by
+    final_hierarchical_image / _text / _all (hierarchical_engine.HierarchicalEngine).
+
+    Takes the eight positionals of the reference's launch (main_both.py:319-327; its constructor wants ten, so the reference's own
+    call raises TypeError) plus the build's keyword arguments.  ``state_dict()`` has the keys and shapes of
+    ``MM_RCA(..., reverse, False, False)``: the RCA blocks are the present-but-unused keys here, the three hierarchical linears the
+    arena parameters, so checkpoints interchange."""
+
+    def __init__(self, n_classes, drop_ratio, image_or_text_dropout_chance, img_prob_dropout, num_neurons_fc, text_model_name, batch_size,
+                 reverse, image_model_name: str = "eff_v2_medium", dtype="bf16x3f", device="cuda", init_seed: int = 0,
+                 build_unused_parameters: bool = True, image_size: Optional[int] = None):
+        from .hierarchical_engine import check_hierarchical_config
+        check_hierarchical_config(text_model_name, image_model_name, int(image_size or 480))       # raises, naming the offending value
+        super().__init__(n_classes, drop_ratio, image_or_text_dropout_chance, img_prob_dropout, num_neurons_fc, text_model_name, batch_size,
+                         reverse, False, False, image_model_name=image_model_name, dtype=dtype, device=device, init_seed=init_seed,
+                         build_unused_parameters=build_unused_parameters, image_size=image_size)
+
+    def _make_engine(self, text_model_name, image_model_name, n_classes, reverse, mode, dtype, device):
+        from .hierarchical_engine import HierarchicalEngine
+        return HierarchicalEngine(text_model_name, image_model_name, n_classes, dtype, device, image_size=self.image_size)
+
+    def _unused_param_entries(self, n_classes, num_neurons_fc, batch_size):
+        return (S.head_used_params(self.engine.d_img, self.engine.d_txt, n_classes, False, False)
+                + S.head_unused_params(self.engine.d_img, self.engine.d_txt, n_classes, num_neurons_fc, batch_size, False, False))
+
+    def forward(self, _input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False):
+        return self._engine_forward(_input_ids, _attention_mask, _images, eval, remove_image, remove_text)

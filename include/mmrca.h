@@ -496,6 +496,36 @@ int mmrca_linear_cls_fwd(const void* feat, int ld, const float* W, const float* 
 int mmrca_linear_cls_bwd(const float* dlogits, const void* feat, int ld, const float* W, float* dW, float* db, void* dfeat,
                          int B, int F, int C, float drop_p, uint64_t seed, int dtype, void* stream);
 
+/* K1c. head of the hierarchical late-fusion model (multimodal_model.Hierarchical; csrc/hier_head.hip).  fp32 arithmetic and fp32
+ * outputs throughout; no atomics, every reduction in a fixed order (bitwise reproducible); weight gradients ACCUMULATE.
+ *
+ * pool: AvgPool2d(k, k) with floor windows (oh = H / k, ow = W / k, the remainder rows / columns are not read) of a stage map in the
+ * NHWC row layout x [B*H*W, C] (`dtype`: bf16 | fp32, sums in fp32), written in NCHW order as fp32:
+ * out[b*ld_out + c*oh*ow + i*ow + j].  k = 1 on a 1 x 1 map copies a [B, C] feature into a column range.  C % 4 == 0.
+ * pool_bwd ADDS d[...] / k^2 into dx [B*H*W, C] (`dtype`) at the covered pixels and does not touch the others. */
+int mmrca_hier_pool_fwd(const void* x, float* out, int ld_out, int B, int H, int W, int C, int k, int dtype, void* stream);
+int mmrca_hier_pool_bwd(const float* d, int ld_d, void* dx, int B, int H, int W, int C, int k, int dtype, void* stream);
+/* norm: raw [B, ld] holds nseg <= 8 segments, columns seg_off[s] .. seg_off[s+1] (HOST array of nseg + 1 increasing offsets).
+ * x[b, i] = raw[b, i] / |segment of i|_2 * keep / (1 - drop_p), inv[b, s] = 1 / |segment s|_2.  Segments 0 .. nseg_a - 1 form group a,
+ * the others group b; keep = the counter hash of (seed_group + mask epoch, b * group width + column inside the group) >= drop_p, so
+ * the two groups draw independent masks (mmrca_seed_epoch_set applies).  No epsilon, as the reference: a zero segment gives
+ * inv = +inf and NaN outputs for that segment (0 * inf), exactly the reference's 0 / 0; the kernel neither hangs nor faults on it.
+ * norm_bwd: draw = the gradient at raw given dx = the gradient at x (same masks, same seeds). */
+int mmrca_hier_norm_fwd(const float* raw, float* x, float* inv, int B, int ld, const int* seg_off, int nseg, int nseg_a,
+                        float drop_p, uint64_t seed_a, uint64_t seed_b, void* stream);
+int mmrca_hier_norm_bwd(const float* dx, const float* raw, const float* inv, float* draw, int B, int ld, const int* seg_off,
+                        int nseg, int nseg_a, float drop_p, uint64_t seed_a, uint64_t seed_b, void* stream);
+/* linear_relu: Y [B, N] (row pitch ldy) = relu(X W^T + b), X [B, K] (row pitch ldx), W [N, K], for batches far smaller than K: the
+ * contraction is split into K / 128 chunks over the whole chip, partial sums through `ws` (mmrca_hier_linear_workspace_bytes, 16-byte
+ * aligned, shared by both directions) and a second launch that adds them in chunk order.  N % 64 == 0, N <= 1024, K % 256 == 0, pitches % 4 == 0, pointers 16-byte aligned.
+ * bwd: dZ = dY * (Y > 0); dW [N, K] += dZ^T X, db [N] += column sums of dZ (samples in order); dX (optional, row pitch lddx) = dZ W,
+ * its sum over n split N / 64 ways through `ws` in the same way (ws may be null when dX is). */
+int64_t mmrca_hier_linear_workspace_bytes(int B, int N, int K);
+int mmrca_hier_linear_relu_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, float* ws,
+                               int64_t ws_bytes, int B, int N, int K, void* stream);
+int mmrca_hier_linear_relu_bwd(const float* dY, int lddy, const float* Y, int ldy, const float* X, int ldx, const float* W,
+                               float* dW, float* db, float* dX, int lddx, float* ws, int64_t ws_bytes, int B, int N, int K, void* stream);
+
 /* K6. weighted, label-smoothed cross entropy (torch.nn.CrossEntropyLoss as built at main_both.py:87-93), mean
  * reduction with the weighted denominator.  loss: fp32[1]; dlogits (optional): fp32 [B,C] scaled by grad_scale. */
 int mmrca_xent_fwd_bwd(const float* logits, const int32_t* labels, const float* class_w, float smoothing,
