@@ -22,55 +22,19 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-import os
-
 from . import lib as L
 
-# dense 3x3 convolutions on tap-major patches (see ConvEncoder._tap_major); "0" = torchvision's channel-major order everywhere
-TAP_MAJOR = os.environ.get("MMRCA_CONV_TAP_MAJOR", "1") == "1"
-PAD_TAP_K = os.environ.get("MMRCA_CONV_PAD_K", "1") == "1"
-# ShuffleNetV2 stride-1 units: branch2's first 1x1 convolution reads the second half of the unit's input in place and its input gradient is
-# written straight into the unit's input gradient (row pitch = the unit's channel count); "0" restores the split / concat copies
-SHUFFLE_INPLACE = os.environ.get("MMRCA_SHUFFLE_INPLACE", "1") == "1"
-# dense 3x3 / stride-1 convolutions as implicit GEMMs (csrc/conv_igemm.hip): no patch matrix, BatchNorm moments in the epilogue;
-# "0" keeps im2row + GEMM everywhere (the A/B switch of DESIGN 3d)
-IGEMM = os.environ.get("MMRCA_CONV_IGEMM", "1") == "1"
-# 1x1 convolutions: BatchNorm moments in the GEMM epilogue (mmrca_gemm_bnstats).  OFF by default: measured 604 -> 592 samples/s on
-# configs[2] -- the separate moments pass reads z straight after the GEMM wrote it (Infinity-Cache hits, ~5 TB/s) and costs less than the
-# extra LDS reduction + barrier per 128x128 tile in the epilogue does.
-FUSE_GEMM_BN = os.environ.get("MMRCA_CONV_FUSE_GEMM_BN", "0") == "1"
-BN_FLAT = os.environ.get("MMRCA_BN_FLAT", "0") == "1"               # flat BatchNorm reductions (csrc/conv.hip, opt-in): need a 16 MiB workspace
-FUSE_SE = os.environ.get("MMRCA_CONV_FUSE_SE", "1") == "1"         # SE backward: dx and the next BatchNorm's backward sums in one pass
-# BatchNorm moments + finish in one launch (mmrca_bn_stats_fused): built, parity-tested, measured SLOWER and off -- the device-scope fence every
-# workgroup needs in front of its ticket waits for its own atomics to complete (they are fire-and-forget otherwise), and the last workgroup's
-# finish is a serial tail: EfficientNetV2-M B = 64 905 -> 692 samples/s, B = 16 482 -> 396, ShuffleNetV2 B = 4 (HIP graph) 655 -> 648
-FUSE_BN_FINISH = os.environ.get("MMRCA_CONV_FUSE_BN_FINISH", "0") == "1"
-FUSE_SE_MLP = os.environ.get("MMRCA_CONV_FUSE_SE_MLP", "1") == "1"   # squeeze-excitation MLP: one launch forward, two backward
-SE_FUSE_MAX = int(os.environ.get("MMRCA_CONV_SE_FUSE_MAX", "160000"))   # c * sq up to which the fused MLP BACKWARD is used (see ConvEncoder._se_fused)
-SE_FUSE_MAX_FWD = int(os.environ.get("MMRCA_CONV_SE_FUSE_MAX_FWD", "300000"))   # ... and the forward (sixteen waves per sample)
-FUSE_RES = os.environ.get("MMRCA_CONV_FUSE_RES", "1") == "1"       # residual connection inside the block's last BatchNorm pass
-IGEMM_DGRAD = os.environ.get("MMRCA_CONV_IGEMM_DGRAD", "1") == "1"
-# Weight gradients of the 1x1 and the implicit-GEMM 3x3 convolutions on a SIDE stream, concurrent with the input-gradient chain they are
-# not part of (see ConvEncoder._wgrad_stream): "1" always, "0" never, "auto" (default) everywhere but inside a HIP-graph capture --
-# measured (EfficientNetV2-M @ 480, bf16x3f, same box): eager B = 64 901.8 -> 927.6 samples/s; the captured B = 16 step 490.9 -> 460-470
-# (every fork / join becomes a cross-branch edge of the graph, ~110 per step).  MMRCA_CONV_SIDE_MAXROWS: only layers with at most that
-# many output rows (B * Ho * Wo).
-SIDE_WGRAD = os.environ.get("MMRCA_CONV_SIDE_WGRAD", "auto")
-SIDE_WGRAD = {"0": False, "1": True}.get(SIDE_WGRAD, "auto")
-SIDE_MAXROWS = int(os.environ.get("MMRCA_CONV_SIDE_MAXROWS", str(1 << 40)))
-# 1x1 weight gradients with at least this many output elements run on the 256x256 split-K slab kernel (mmrca_gemm_splitk on ragged
-# output shapes) instead of 128x128 tiles + fp32 atomics.  Isolated (tools/conv_wgrad_bench.py, us, atomics / slabs, B = 64 | B = 16):
-# 3072 x 512: 98 / 59 | 60 / 34; 512 x 3072: 89 / 59 | 58 / 34; 176 x 1056: 61 / 60 | 29 / 38; 304 x 1824: 46 / 50 | 24 / 32;
-# 160 x 640: 50 / 57 | 26 / 42; 48 x 192 (K = 921,600): 92 / 166 | 33 / 99 -- the slabs pay for whole 256x256 tiles and a second launch,
-# which only the widest layers (EfficientNetV2-M stage 7, -L stages 6-7) win back.  "0" = never.
-WGRAD_SLAB_MIN_ELEMS = int(os.environ.get("MMRCA_CONV_WGRAD_SLAB_MIN", "1000000"))
-# train-mode BatchNorm forward in two launches instead of three: the finish step (sums -> mean / rstd, running statistics) inside the apply
-# pass (mmrca_bn_moments + mmrca_bn_act_fwd_fin; bf16, channel counts that are multiples of 8).  OFF by default: parity-green and measured
-# at +0.1 .. +2.2 % (EfficientNetV2-M B = 16: 517.3 / 509.5 -> 529.0 / 509.9 samples/s; B = 64 938.0 / 943.6 -> 941.8 / 951.8; ShuffleNetV2 B = 4
-# under a HIP graph 654 -> 660; configs[2] 649 -> 647) -- inside the run-to-run noise except for the graph-replayed step: not worth a
-# default-on change to the BatchNorm path in this round (tools/bn_fold_ab.sh)
-BN_FOLD = os.environ.get("MMRCA_CONV_BN_FOLD", "0") == "1"
-SIDE_DW = os.environ.get("MMRCA_CONV_SIDE_DW", "1") == "1"       # ... and the depthwise convolutions' weight gradients with them
+# Tunables of the conv path: attributes that tests and bench.py set, and tuned thresholds.  Nothing on this path reads the environment (the
+# settled A/B switches and their measured reasons: DESIGN 3d, "Retired conv / BatchNorm switches").
+TAP_MAJOR = True                 # dense 3x3 convolutions on tap-major patches (see ConvEncoder._tap_major); False = torchvision's channel-major order
+# weight gradients of the 1x1, implicit-GEMM 3x3 and depthwise convolutions on a side stream beside the input-gradient chain (see
+# ConvEncoder._wgrad_stream): True always, False never, "auto" everywhere but inside a HIP-graph capture
+SIDE_WGRAD = "auto"
+SIDE_MAXROWS = 1 << 40           # ... only for layers with at most that many output rows (B * Ho * Wo)
+BN_FOLD = False                  # train-mode BatchNorm forward in two launches (mmrca_bn_moments + mmrca_bn_act_fwd_fin): parity-tested, gain inside the noise
+SE_FUSE_MAX = 160000             # c * sq up to which the fused squeeze-excitation MLP BACKWARD is used (see ConvEncoder._se_fused)
+SE_FUSE_MAX_FWD = 300000         # ... and the forward (sixteen waves per sample)
+WGRAD_SLAB_MIN_ELEMS = 1000000   # 1x1 weight gradients with at least this many output elements run on the 256x256 split-K slab kernel
 
 ROWPAD = 256
 
@@ -338,10 +302,9 @@ class ConvEncoder:
             self._bn_arena = torch.zeros(self.BN_ARENA_FLOATS, dtype=torch.float32, device=self.o.device)
         off = self._bn_off.get(u.bn_key)
         c = u.cout
-        nt = _ru((c + 63) // 64, 4)                          # tickets of the fused statistics launch (mmrca_bn_stats_fused), cleared with the rest
         if off is None:
             off = self._bn_used
-            self._bn_used += 7 * _ru(c, 4) + nt             # (16-byte aligned slices; the last three: s1 | s2 | shift of _bn_sums)
+            self._bn_used += 7 * _ru(c, 4)                  # (16-byte aligned slices; the last three: s1 | s2 | shift of _bn_sums)
             if self._bn_used > self.BN_ARENA_FLOATS:
                 raise L.MmrcaError("conv_engine: BatchNorm arena exhausted")
             self._bn_off[u.bn_key] = off
@@ -351,12 +314,8 @@ class ConvEncoder:
         """(s1, s2, shift) of the folded forward (BN_FOLD): three fp32 [C] vectors behind the layer's other slices, cleared with them"""
         self._bn_slices(u)
         c4 = _ru(u.cout, 4)
-        off = self._bn_off[u.bn_key] + 4 * c4 + _ru((u.cout + 63) // 64, 4)
+        off = self._bn_off[u.bn_key] + 4 * c4
         return tuple(self._bn_arena[off + k * c4: off + k * c4 + u.cout] for k in range(3))
-
-    def _bn_tickets(self, u: "_Unit"):
-        off = self._bn_off[u.bn_key] + 4 * _ru(u.cout, 4)
-        return self._bn_arena[off: off + _ru((u.cout + 63) // 64, 4)].view(torch.int32)
 
     def _bn_scratch(self, u: "_Unit"):
         """the backward sums of u, clear: by forward()'s fill, or -- a second backward over the same forward -- by a fill of its own"""
@@ -365,12 +324,6 @@ class ConvEncoder:
             scratch.zero_()
         self._bn_bwd_seen.add(u.bn_key)
         return scratch
-
-    def _bn_ws(self):
-        """16 MiB of fp32 words for the flat BatchNorm reductions (one 64-byte record per streaming thread, csrc/conv.hip)"""
-        if not BN_FLAT or self.cdtype != torch.bfloat16:      # the flat reductions are opt-in (MMRCA_BN_FLAT=1): no workspace otherwise
-            return None
-        return self.buf("tmp.bnws", 4096, 1024, torch.float32)
 
     def release(self):
         self._bufs.clear()
@@ -402,16 +355,13 @@ class ConvEncoder:
         % 64), input gradient (N = patch width % 128) and weight gradient (N % 128); 9*cin itself is 576 / 864 in
         EfficientNetV2-L's stages 2 / 3, which left them on the general kernel at a fifth of the rate (+11 % / +4 % padded work)."""
         K = 9 * u.cin
-        return _ru(K, 128) if (u.cout % 128 == 0 and PAD_TAP_K) else K
+        return _ru(K, 128) if u.cout % 128 == 0 else K
 
     def _igemm(self, u: "_Unit") -> bool:
         """stride-1 dense 3x3 convolutions with cin % 8 == 0 run without a patch matrix (mmrca_conv3x3_fwd / _wgrad); channel counts
-        that are not multiples of 32 (EfficientNetV2-M: 24 / 48 / 80) are padded to one per tap in the weight copy only"""
-        return IGEMM and self._tap_major(u) and u.k == 3 and not u.dw and u.stride == 1 and u.cin % 8 == 0 and u.cout % 8 == 0
-
-    def _igemm_dgrad(self, u: "_Unit") -> bool:
-        """... and their input gradient is the same kernel on dz with flipped, transposed weights when cout % 32 == 0"""
-        return IGEMM_DGRAD and self._igemm(u)
+        that are not multiples of 32 (EfficientNetV2-M: 24 / 48 / 80) are padded to one per tap in the weight copy only; their input
+        gradient is the same kernel on dz with flipped, transposed weights"""
+        return self._tap_major(u) and u.k == 3 and not u.dw and u.stride == 1 and u.cin % 8 == 0 and u.cout % 8 == 0
 
     def _tap_weight_igemm(self, u: "_Unit", w, flip=False):
         """weight copy of the implicit-GEMM kernels: [cout, 9, Cp] with Cp = cin rounded up to 32 (zero pad channels); flip: the
@@ -446,22 +396,14 @@ class ConvEncoder:
         z = self.buf(tag + ".z", rows, u.cout)
         w = self.W(u.conv_key + ".weight")
         fused_stats = False
-        sums = None
         fold = False
         if u.dw and u.k == 5:
             L.dwconv5x5_fwd(x, w, z, B, H, Wd, u.cin, u.stride, dt)
         elif u.dw:
             L.dwconv3x3_fwd(x, w, z, B, H, Wd, u.cin, u.stride, dt)
         elif u.k == 1:
-            if train and FUSE_GEMM_BN and self.o.gemm_impl == L.IMPL_AUTO and L.gemm_bnstats_ok(rows, u.cout, u.cin, dt):
-                # BatchNorm moments of z in the GEMM's epilogue: shifted sums per 128-row block (shift = the running mean)
-                nsl = (rows + 127) // 128
-                sums = (self.buf("tmp.bnsum.s1", nsl, u.cout, torch.float32), self.buf("tmp.bnsum.s2", nsl, u.cout, torch.float32), nsl)
-                L.gemm_bnstats(x, w, z, M=rows, N=u.cout, K=u.cin, lda=u.cin, ldb=u.cin, ldc=u.cout, dtype=dt,
-                               shift=self.buffers[u.bn_key + ".running_mean"], s1=sums[0], s2=sums[1])
-            else:
-                # ld_in: x is a column window of a wider row buffer (ShuffleNetV2's second half, read in place instead of through a split copy)
-                L.gemm(x, w, z, M=rows, N=u.cout, K=u.cin, lda=(ld_in or u.cin), ldb=u.cin, ldc=u.cout, dtype=dt, impl=self.o.gemm_impl)
+            # ld_in: x is a column window of a wider row buffer (ShuffleNetV2's second half, read in place instead of through a split copy)
+            L.gemm(x, w, z, M=rows, N=u.cout, K=u.cin, lda=(ld_in or u.cin), ldb=u.cin, ldc=u.cout, dtype=dt, impl=self.o.gemm_impl)
         elif self._igemm(u):
             ns = L.conv3x3_stat_slots(B, H, Wd)
             parts = None
@@ -486,18 +428,14 @@ class ConvEncoder:
         rm, rv = self.buffers[u.bn_key + ".running_mean"], self.buffers[u.bn_key + ".running_var"]
         if fused_stats:
             L.conv_bn_finish(parts, B, H, Wd, mean, rstd, rm, rv, u.cout, u.eps, u.momentum)
-        elif sums is not None:
-            L.bn_finish_sums(sums[0], sums[1], rm, sums[2], rows, mean, rstd, rm, rv, u.cout, u.eps, u.momentum)
         else:
-            fold = BN_FOLD and train and not BN_FLAT and not FUSE_BN_FINISH and L.bn_fold_ok(u.cout, u.cout, dt)
+            fold = BN_FOLD and train and L.bn_fold_ok(u.cout, u.cout, dt)
             if fold:
                 s1, s2, shift = self._bn_sums(u)
                 L.bn_moments(z, s1, s2, shift, rows, u.cout, u.cout, dt)
             else:
-                fuse = FUSE_BN_FINISH and train and self.cdtype == torch.bfloat16 and u.cout % 8 == 0 and not BN_FLAT
-                L.bn_stats(z, mean, rstd, rm, rv, rows, u.cout, u.cout, u.eps, u.momentum if train else 0.0, train, dt, ws=self._bn_ws(), prezeroed=True,
-                           tickets=self._bn_tickets(u) if fuse else None)
-        fused_res = res is not None and FUSE_RES and self.cdtype == torch.bfloat16 and u.cout % 8 == 0
+                L.bn_stats(z, mean, rstd, rm, rv, rows, u.cout, u.cout, u.eps, u.momentum if train else 0.0, train, dt, prezeroed=True)
+        fused_res = res is not None and self.cdtype == torch.bfloat16 and u.cout % 8 == 0
         if fold:
             y = out if fused_res else self.buf(tag + ".y", rows, u.cout)
             L.bn_act_fwd_fin(z, s1, s2, shift, self.W(u.bn_key + ".weight"), self.W(u.bn_key + ".bias"), res if fused_res else None,
@@ -538,9 +476,9 @@ class ConvEncoder:
         return self._scratch("splitk", L.SPLITK_WS_BYTES, per_stream=True)
 
     def _dw_ws(self):
-        """partial sums of the depthwise weight gradients (csrc/conv.hip, written before they are read): 3x3 at most 196,608 threads x
+        """partial sums of the depthwise weight gradients (csrc/conv.hip, written before they are read): 3x3 at most 65,536 threads x
         288 B; 5x5 at most 262,144 threads x 160 B + the fixed-order reduction's 16 x C x 100 B"""
-        return self._scratch("dw", 64 << 20, per_stream=True).view(torch.float32)      # (per stream: MMRCA_CONV_SIDE_MAXROWS can leave some layers on the main one)
+        return self._scratch("dw", 64 << 20, per_stream=True).view(torch.float32)      # (per stream: SIDE_MAXROWS can leave some layers on the main one)
 
     def _side_on(self, rows: int) -> bool:
         if not SIDE_WGRAD or rows > SIDE_MAXROWS or torch.device(self.o.device).type != "cuda":
@@ -584,14 +522,14 @@ class ConvEncoder:
         scratch = self._bn_slices(u)[1] if sums_ready else self._bn_scratch(u)      # this layer's backward sums (clear since forward(), or filled by se_dx)
         L.bn_act_bwd(dy, sv["z"], sv["mean"], sv["rstd"], self.W(u.bn_key + ".weight"), self.W(u.bn_key + ".bias"), dz,
                      self.G(u.bn_key + ".weight"), self.G(u.bn_key + ".bias"), scratch, rows, u.cout, u.act, sv["train"], dt,
-                     sums_ready=sums_ready, ws=self._bn_ws(), prezeroed=True)
+                     sums_ready=sums_ready, prezeroed=True)
         w, gw = self.W(u.conv_key + ".weight"), self.G(u.conv_key + ".weight")
         rows_in = B * H * Wd
         dx = self.buf(f"{tag}.dx.{u.cin}.{rows_in}", rows_in, u.cin) if need_dx else None
         rows_k = _ru(rows, 64)                       # the contraction of the weight gradient runs over whole 64-row steps (zero pad rows)
         if u.dw:
             dw_bwd = L.dwconv5x5_bwd if u.k == 5 else L.dwconv3x3_bwd
-            if SIDE_DW and self._side_on(rows):
+            if self._side_on(rows):
                 # (the library runs the input gradient and the weight gradient as separate launches anyway: one call for each)
                 with self._wgrad_stream(dz_key, rows):
                     dw_bwd(dz, sv["x"], w, None, gw, B, H, Wd, u.cin, u.stride, dt, ws=self._dw_ws())
@@ -621,15 +559,8 @@ class ConvEncoder:
                 L.conv3x3_wgrad(dz, sv["x"], gwt, B, H, Wd, u.cin, u.cout, dt)
                 gw.view(u.cout, u.cin, 9).add_(gwt.view(u.cout, 9, u.cin).transpose(1, 2))
             if need_dx:
-                if self._igemm_dgrad(u):
-                    # dx = conv3x3(dz, w'), w'[ci, tap', co] = w[co, ci, 8 - tap']
-                    L.conv3x3_fwd(dz, self._tap_weight_igemm(u, w, flip=True), dx, B, H, Wd, u.cout, u.cin, dt)
-                else:
-                    Kp = self._tap_k(u)
-                    col = self.buf("tmp.col", rows, Kp)
-                    L.gemm(dz, self._tap_weight(u, w), col, M=rows, N=Kp, K=u.cout, lda=u.cout, ldb=Kp, ldc=Kp, a_layout=L.ROWK,
-                           b_layout=L.KROW, dtype=dt, impl=self.o.gemm_impl)
-                    L.col2im3x3_tap(col, dx, B, H, Wd, u.cin, u.stride, Kp, dt)
+                # dx = conv3x3(dz, w'), w'[ci, tap', co] = w[co, ci, 8 - tap']
+                L.conv3x3_fwd(dz, self._tap_weight_igemm(u, w, flip=True), dx, B, H, Wd, u.cout, u.cin, dt)
         else:
             tap = self._tap_major(u)
             K = self._tap_k(u) if tap else 9 * u.cin
@@ -662,7 +593,7 @@ class ConvEncoder:
         multiple of 8 (EfficientNetV2-M: 20 / 44 / 76 -> the general GEMM kernel).  Measured (tools/se_bench.py, us, fused vs GEMM
         sequence): forward 1824 x 76: 23 vs 75, 2304 x 96: 32 vs 44, 3072 x 128: 51 vs 46, 3840 x 160: 79 vs 62; backward 1824 x 76: 48 vs 137,
         2304 x 96: 76 vs 66.  Forward and backward choose independently (both forms save the same tensors)."""
-        return (FUSE_SE_MLP and se.act1 == L.CONV_SILU and se.act2 == L.CONV_SIGMOID and se.c % 4 == 0 and se.sq % 4 == 0
+        return (se.act1 == L.CONV_SILU and se.act2 == L.CONV_SIGMOID and se.c % 4 == 0 and se.sq % 4 == 0
                 and (se.c * se.sq <= limit or se.sq % 8 != 0))
 
     def _se_fwd(self, se: _SE, x, B, HW, tag, save):
@@ -690,7 +621,7 @@ class ConvEncoder:
         HW = sv["HW"]
         g = lambda s, r, c: self.buf(gp + ".se" + s + f".{c}", r, c)
         dx, ds = self.buf(f"{gp}.se.dx.{se.c}.{B * HW}", B * HW, se.c), g(".ds", B, se.c)
-        fused = FUSE_SE and self.cdtype == torch.bfloat16 and se.c % 8 == 0
+        fused = self.cdtype == torch.bfloat16 and se.c % 8 == 0
         L.se_scale_bwd(dy, sv["x"], sv["s"], None if fused else dx, ds, B, HW, se.c, dt)
         ds_pre, dh_pre, dpool = g(".dspre", B, se.c), g(".dhpre", B, se.sq), g(".dpool", B, se.c)
         if self._se_fused(se, SE_FUSE_MAX):        # the whole MLP backward: a per-sample chain + one launch for the batch sums (six launches otherwise)
@@ -811,7 +742,7 @@ class ConvEncoder:
                 bf = Cc // 2
                 rows = B * h * w
                 bs = dict(b2=[], H=h, W=w)
-                inplace = SHUFFLE_INPLACE and blk["b2"][0].k == 1 and not blk["b2"][0].dw and not (train and FUSE_GEMM_BN)
+                inplace = blk["b2"][0].k == 1 and not blk["b2"][0].dw
                 if inplace:                      # branch2's first 1x1 convolution reads x[:, bf:] where it lies (row pitch Cc): no split copy
                     y2, h2, w2 = x[:, bf:], h, w
                 else:

@@ -454,56 +454,6 @@ dwconv3x3_fwd_v8_k(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w, b
   *reinterpret_cast<cv_b8*>(y + op * C + c0) = o;
 }
 
-// Stride-1 layers (all but three of EfficientNetV2's depthwise convolutions): a thread owns FOUR consecutive output pixels of a
-// row for its 8 channels -- the 72 weights are fetched once per four outputs and the 3 x 6 input window serves all of them
-// (6.75 sixteen-byte loads per output instead of 18).  FLIP = the input gradient (the same correlation with the kernel turned
-// by 180 degrees).  Per output the products are added in the same (ky, kx) order as in the one-pixel kernels: identical bits.
-template <bool FLIP>
-__global__ void __launch_bounds__(256)
-dw3x3_s1_strip_v8_k(const bf16_t* __restrict__ in, const bf16_t* __restrict__ w, bf16_t* __restrict__ out, int B, int H, int W, int C) {
-  const int C8 = C >> 3, XG = (W + 3) >> 2;
-  const int64_t idx = xcd_block() * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)B * H * XG * C8) return;
-  const int c0 = (int)(idx % C8) * 8;
-  const int64_t g = idx / C8;
-  const int x0 = (int)(g % XG) * 4, y = (int)((g / XG) % H), b = (int)(g / ((int64_t)XG * H));
-  float wf[8][9];
-  dw_load_w8(w, c0, wf);
-  float s[4][8];
-#pragma unroll
-  for (int o = 0; o < 4; ++o)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s[o][j] = 0.f;
-#pragma unroll
-  for (int ky = 0; ky < 3; ++ky) {
-    const int iy = y + ky - 1;
-    if (iy < 0 || iy >= H) continue;
-    const bf16_t* row = in + ((int64_t)b * H + iy) * W * C + c0;
-#pragma unroll
-    for (int col = 0; col < 6; ++col) {
-      const int ix = x0 + col - 1;
-      if (ix < 0 || ix >= W) continue;
-      const cv_b8 v = *reinterpret_cast<const cv_b8*>(row + (int64_t)ix * C);
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        const int kx = col - o;
-        if (kx < 0 || kx > 2) continue;
-        const int tap = FLIP ? (2 - ky) * 3 + (2 - kx) : ky * 3 + kx;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) s[o][j] = fmaf((float)v[j], wf[j][tap], s[o][j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 0; o < 4; ++o) {
-    if (x0 + o >= W) continue;
-    cv_b8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (bf16_t)s[o][j];
-    *reinterpret_cast<cv_b8*>(out + (((int64_t)b * H + y) * W + x0 + o) * C + c0) = r;
-  }
-}
-
 __global__ void __launch_bounds__(256)
 dwconv3x3_bwd_data_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ w, bf16_t* __restrict__ dx, int B, int H, int W, int C,
                         int Ho, int Wo, int stride) {
@@ -589,78 +539,14 @@ dwconv3x3_bwd_weight_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restric
   }
 }
 
-// stride 1: four consecutive output pixels of a row per thread and iteration -- 4 loads of dy and the 3 x 6 window of x serve 36
-// (pixel, tap) pairs (5.5 sixteen-byte loads per pixel instead of 10); same reduction afterwards
-__global__ void __launch_bounds__(256)
-dwconv3x3_bwd_weight_s1_strip_v8_k(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ dw, int B, int H, int W,
-                                   int C, int64_t grp_per_block) {
-  __shared__ float red[4][8][73];
-  const int cg = threadIdx.x & 7, pl = threadIdx.x >> 3;
-  const int c0 = blockIdx.x * 64 + cg * 8, XG = (W + 3) >> 2;
-  float acc[8][9];
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-#pragma unroll
-    for (int t = 0; t < 9; ++t) acc[j][t] = 0.f;
-  const int64_t ngrp = (int64_t)B * H * XG;
-  const int64_t g0 = (int64_t)blockIdx.y * grp_per_block;
-  const int64_t g1 = g0 + grp_per_block < ngrp ? g0 + grp_per_block : ngrp;
-  if (c0 < C) {
-    for (int64_t g = g0 + pl; g < g1; g += 32) {
-      const int x0 = (int)(g % XG) * 4, y = (int)((g / XG) % H), b = (int)(g / ((int64_t)XG * H));
-      float gv[4][8];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        cv_b8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (bf16_t)0.f;
-        if (x0 + o < W) v = *reinterpret_cast<const cv_b8*>(dy + (((int64_t)b * H + y) * W + x0 + o) * C + c0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) gv[o][j] = (float)v[j];
-      }
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-        const int iy = y + ky - 1;
-        if (iy < 0 || iy >= H) continue;
-        const bf16_t* row = x + ((int64_t)b * H + iy) * W * C + c0;
-#pragma unroll
-        for (int col = 0; col < 6; ++col) {
-          const int ix = x0 + col - 1;
-          if (ix < 0 || ix >= W) continue;
-          const cv_b8 xv = *reinterpret_cast<const cv_b8*>(row + (int64_t)ix * C);
-#pragma unroll
-          for (int o = 0; o < 4; ++o) {
-            const int kx = col - o;
-            if (kx < 0 || kx > 2) continue;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j][ky * 3 + kx] = fmaf(gv[o][j], (float)xv[j], acc[j][ky * 3 + kx]);
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      float v = acc[j][t];
-      v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
-      if ((threadIdx.x & 63) < 8) red[threadIdx.x >> 6][cg][j * 9 + t] = v;
-    }
-  __syncthreads();
-  for (int e = threadIdx.x; e < 8 * 72; e += 256) {
-    const int g = e / 72, r = e % 72;
-    const int c = blockIdx.x * 64 + g * 8 + r / 9;
-    if (c < C) atomicAdd(dw + (int64_t)c * 9 + r % 9, (red[0][g][r] + red[1][g][r]) + (red[2][g][r] + red[3][g][r]));
-  }
-}
-
-
-// Round 3: the same with TWO output rows per thread and 32-bit index arithmetic.  The kernels above were neither HBM- nor
-// L2-bound (2.1-2.4 TB/s, 47 % VALU-busy): a third of their ~970 VALU instructions per thread were 64-bit divisions / address
+// Stride-1 layers (all but three of EfficientNetV2's depthwise convolutions): a thread owns a strip of TWO rows x FOUR consecutive
+// output pixels for its 8 channels, with 32-bit index arithmetic.  The one-row, 64-bit-indexed strip kernels this replaced were neither
+// HBM- nor L2-bound (2.1-2.4 TB/s, 47 % VALU-busy): a third of their ~970 VALU instructions per thread were 64-bit divisions / address
 // multiplies of the index decomposition, another quarter the bf16 -> fp32 conversion of the 72 weights, repeated for every
-// four outputs.  Here: unsigned 32-bit indices (tensors below 4 GiB: the launcher checks), eight outputs per thread (the 4 x 6
-// input window serves 72 (pixel, tap) pairs: 3 sixteen-byte loads per output instead of 4.5; weights converted once per eight).
+// four outputs.  Here: unsigned 32-bit indices (tensors below 4 GiB: the launcher checks; larger ones take the one-pixel kernels
+// above), eight outputs per thread (the 4 x 6 input window serves 72 (pixel, tap) pairs: 3 sixteen-byte loads per output instead of
+// 4.5; weights converted once per eight).  FLIP = the input gradient (the same correlation with the kernel turned by 180 degrees).
+// Per output the products are added in the same (ky, kx) order as in the one-pixel kernels: identical bits.
 template <bool FLIP>
 __global__ void __launch_bounds__(256)
 dw3x3_s1_strip2_v8_k(const bf16_t* __restrict__ in, const bf16_t* __restrict__ w, bf16_t* __restrict__ out, unsigned B, unsigned H, unsigned W,
@@ -949,31 +835,19 @@ static bool dw_v8_ok(int C, int dtype, const void* a, const void* b, const void*
   return dtype == MMRCA_BF16 && C % 8 == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
 }
 
-static const bool g_dw_flat = !(getenv("MMRCA_DW_WG_FLAT") && atoi(getenv("MMRCA_DW_WG_FLAT")) == 0);
-static const int g_dw_flat_rows = getenv("MMRCA_DW_WG_FLAT_ROWS") ? atoi(getenv("MMRCA_DW_WG_FLAT_ROWS")) : 2;
-// threads of the streaming weight gradient = what is resident at once: the two-row form needs > 128 registers (one wave per SIMD:
-// 256 CUs x 4 x 64 lanes), the one-row form fits three
-static const int g_dw_flat_threads = getenv("MMRCA_DW_WG_FLAT_THREADS") ? atoi(getenv("MMRCA_DW_WG_FLAT_THREADS")) : (g_dw_flat_rows == 2 ? 65536 : 196608);
-static const int g_dw_blocks_ws = getenv("MMRCA_DW_WG_BLOCKS_WS") ? atoi(getenv("MMRCA_DW_WG_BLOCKS_WS")) : 768;
-static const int g_dw_blocks = getenv("MMRCA_DW_WG_BLOCKS") ? atoi(getenv("MMRCA_DW_WG_BLOCKS")) : 768;
-static const bool g_dw_strip2 = !(getenv("MMRCA_DW_STRIP2") && atoi(getenv("MMRCA_DW_STRIP2")) == 0);
-static const bool g_dw_strip = !(getenv("MMRCA_DW_STRIP") && atoi(getenv("MMRCA_DW_STRIP")) == 0);
+// threads of the streaming weight gradient = what is resident at once: its two-row groups need > 128 registers (one wave per SIMD:
+// 256 CUs x 4 x 64 lanes)
+static const int DW_FLAT_THREADS = 65536;
+static const int DW_WG_BLOCKS = 768;       // blocks of the slice form, with or without a workspace: ~3 per CU
 extern "C" int mmrca_dwconv3x3_fwd(const void* x, const void* w, void* y, int B, int H, int W, int C, int stride, int dtype, void* stream) {
   MMRCA_REQUIRE(x && w && y && B > 0 && H > 0 && W > 0 && C > 0 && (stride == 1 || stride == 2), "dwconv3x3_fwd: bad arguments");
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const bool small32 = (int64_t)B * H * W * C * 2 < (1ll << 32);          // 32-bit element offsets in the two-row strip kernels
-  if (dw_v8_ok(C, dtype, x, w, y) && stride == 1 && g_dw_strip && g_dw_strip2 && small32) {
+  if (dw_v8_ok(C, dtype, x, w, y) && stride == 1 && small32) {
     const int64_t n = (int64_t)B * ((H + 1) / 2) * ((W + 3) / 4) * (C / 8);
     hipLaunchKernelGGL(dw3x3_s1_strip2_v8_k<false>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                        (const bf16_t*)w, (bf16_t*)y, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)C);
     MMRCA_CHECK_LAUNCH("dwconv3x3_fwd(strip2)");
-    return 0;
-  }
-  if (dw_v8_ok(C, dtype, x, w, y) && stride == 1 && g_dw_strip) {
-    const int64_t n = (int64_t)B * H * ((W + 3) / 4) * (C / 8);
-    hipLaunchKernelGGL(dw3x3_s1_strip_v8_k<false>, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                       (const bf16_t*)w, (bf16_t*)y, B, H, W, C);
-    MMRCA_CHECK_LAUNCH("dwconv3x3_fwd(strip)");
     return 0;
   }
   if (dw_v8_ok(C, dtype, x, w, y)) {
@@ -1005,16 +879,11 @@ extern "C" int mmrca_dwconv3x3_bwd_ws(const void* dy, const void* x, const void*
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
   const bool small32 = (int64_t)B * H * W * C * 2 < (1ll << 32);
-  if (dx && dw_v8_ok(C, dtype, dy, w, dx) && stride == 1 && g_dw_strip && g_dw_strip2 && small32) {
+  if (dx && dw_v8_ok(C, dtype, dy, w, dx) && stride == 1 && small32) {
     const int64_t n = (int64_t)B * ((H + 1) / 2) * ((W + 3) / 4) * (C / 8);
     hipLaunchKernelGGL(dw3x3_s1_strip2_v8_k<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w,
                        (bf16_t*)dx, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)C);
     MMRCA_CHECK_LAUNCH("dwconv3x3_bwd(data,strip2)");
-  } else if (dx && dw_v8_ok(C, dtype, dy, w, dx) && stride == 1 && g_dw_strip) {
-    const int64_t n = (int64_t)B * H * ((W + 3) / 4) * (C / 8);
-    hipLaunchKernelGGL(dw3x3_s1_strip_v8_k<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w,
-                       (bf16_t*)dx, B, H, W, C);
-    MMRCA_CHECK_LAUNCH("dwconv3x3_bwd(data,strip)");
   } else if (dx && dw_v8_ok(C, dtype, dy, w, dx)) {
     const int64_t n8 = (int64_t)B * H * W * (C / 8);
     hipLaunchKernelGGL(dwconv3x3_bwd_data_v8_k, dim3(blocks_for(n8, 256)), dim3(256), 0, st, (const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx,
@@ -1035,29 +904,25 @@ extern "C" int mmrca_dwconv3x3_bwd_ws(const void* dy, const void* x, const void*
     int64_t nblk = npix / 32 > 0 ? npix / 32 : 1;
     if (nblk > 2048 / cslices) nblk = 2048 / cslices > 0 ? 2048 / cslices : 1;
     const int64_t per = (npix + nblk - 1) / nblk;
-    if (dw_v8_ok(C, dtype, dy, x, dw) && stride == 1 && g_dw_strip && g_dw_strip2 && small32) {
+    if (dw_v8_ok(C, dtype, dy, x, dw) && stride == 1 && small32) {
       const int64_t ngrp = (int64_t)B * H * ((W + 3) / 4);
       const int slices = (C / 8 + 63) / 64;                  // 64 channel groups (512 channels) per block
       const int64_t row_bytes = (int64_t)slices * 4608 * 4;  // one workspace row: every block of one pixel range
       const bool use_ws = ws && (((uintptr_t)ws) & 15) == 0 && ws_bytes >= 8 * row_bytes;
-      int64_t nb = (use_ws ? g_dw_blocks_ws : g_dw_blocks) / slices;   // blocks in all: ~12 per CU with a workspace, ~3 when every block ends in 4,608 atomics
+      int64_t nb = DW_WG_BLOCKS / slices;
       if (use_ws && nb > ws_bytes / row_bytes) nb = ws_bytes / row_bytes;
       if (nb > ngrp / 8) nb = ngrp / 8 > 0 ? ngrp / 8 : 1;
       const int64_t gper = (ngrp + nb - 1) / nb;
       const unsigned nranges = (unsigned)((ngrp + gper - 1) / gper);
-      // streaming form: lanes = as many pixel lanes as threads fit on the chip at three waves per SIMD, bounded by the workspace
+      // streaming form: lanes = as many pixel lanes as threads fit on the chip at one wave per SIMD, bounded by the workspace
       const int64_t C8 = C / 8;
-      int64_t lanes = g_dw_flat ? (int64_t)g_dw_flat_threads / C8 : 0;
-      const int64_t ngrp_f = g_dw_flat_rows == 2 ? (int64_t)B * ((H + 1) / 2) * ((W + 3) / 4) : ngrp;
+      int64_t lanes = (int64_t)DW_FLAT_THREADS / C8;
+      const int64_t ngrp_f = (int64_t)B * ((H + 1) / 2) * ((W + 3) / 4);      // (its groups are two rows x four pixels)
       if (lanes > ngrp_f) lanes = ngrp_f;
       if (ws && lanes * C8 * 72 * 4 > ws_bytes) lanes = ws_bytes / (C8 * 72 * 4);
       if (ws && (((uintptr_t)ws) & 15) == 0 && lanes >= 64) {
-        if (g_dw_flat_rows == 2)
-          hipLaunchKernelGGL(dwconv3x3_bwd_weight_s1_flat_v8_k<2>, dim3(blocks_for(lanes * C8, 256)), dim3(256), 0, st, (const bf16_t*)dy,
-                             (const bf16_t*)x, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)C, (unsigned)lanes, (float*)ws);
-        else
-          hipLaunchKernelGGL(dwconv3x3_bwd_weight_s1_flat_v8_k<1>, dim3(blocks_for(lanes * C8, 256)), dim3(256), 0, st, (const bf16_t*)dy,
-                             (const bf16_t*)x, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)C, (unsigned)lanes, (float*)ws);
+        hipLaunchKernelGGL(dwconv3x3_bwd_weight_s1_flat_v8_k<2>, dim3(blocks_for(lanes * C8, 256)), dim3(256), 0, st, (const bf16_t*)dy,
+                           (const bf16_t*)x, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)C, (unsigned)lanes, (float*)ws);
         hipLaunchKernelGGL(dw_wg_reduce_k, dim3((unsigned)((C * 9 + 63) / 64), 8), dim3(256), 0, st, (const float*)ws, dw, (int)lanes, C * 9,
                            (int64_t)C * 9);
       } else if (use_ws) {
@@ -1070,16 +935,6 @@ extern "C" int mmrca_dwconv3x3_bwd_ws(const void* dy, const void* x, const void*
                            (const bf16_t*)dy, (const bf16_t*)x, dw, (unsigned)B, (unsigned)H, (unsigned)W, (unsigned)C, (unsigned)gper, (float*)nullptr);
       }
       MMRCA_CHECK_LAUNCH("dwconv3x3_bwd(weight,strip2)");
-      return 0;
-    }
-    if (dw_v8_ok(C, dtype, dy, x, dw) && stride == 1 && g_dw_strip) {
-      const int64_t ngrp = (int64_t)B * H * ((W + 3) / 4);
-      int64_t nb = ngrp / 128 > 0 ? ngrp / 128 : 1;
-      if (nb > 1024) nb = 1024;
-      const int64_t gper = (ngrp + nb - 1) / nb;
-      hipLaunchKernelGGL(dwconv3x3_bwd_weight_s1_strip_v8_k, dim3((unsigned)((C + 63) / 64), (unsigned)((ngrp + gper - 1) / gper)), dim3(256), 0, st,
-                         (const bf16_t*)dy, (const bf16_t*)x, dw, B, H, W, C, gper);
-      MMRCA_CHECK_LAUNCH("dwconv3x3_bwd(weight,strip)");
       return 0;
     }
     if (dw_v8_ok(C, dtype, dy, x, dw)) {
@@ -1652,32 +1507,6 @@ __device__ __forceinline__ void col_reduce8(float (&acc)[NV][8], float (*red)[8]
   }
 }
 
-template <bool CENTERED>
-__global__ void __launch_bounds__(256)
-col_moment_v8_k(const bf16_t* __restrict__ x, const float* __restrict__ mean, float* __restrict__ out, int64_t rows, int C, int64_t ld,
-                int64_t rows_per_block, float mscale) {
-  __shared__ float red[4][8][9];
-  const int cg = threadIdx.x & 7, rl = threadIdx.x >> 3;
-  const int c0 = blockIdx.x * 64 + cg * 8;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
-  float acc[1][8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[0][j] = 0.f;
-  if (c0 < C) {
-    float m[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m[j] = CENTERED ? mean[c0 + j] * mscale : 0.f;
-    for (int64_t r = r0 + rl; r < r1; r += 32) {
-      const cm_b8 v = *reinterpret_cast<const cm_b8*>(x + r * ld + c0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float d = (float)v[j] - m[j]; acc[0][j] += CENTERED ? d * d : d; }
-    }
-  }
-  float* const outs[1] = {out};
-  col_reduce8<1>(acc, red, outs, blockIdx.x, C);
-}
-
 // Both moments in ONE pass over x (bf16 fast path of mmrca_bn_stats): sums of d and d*d with d = x - shift[c] (fp32 sums).
 // Any shift within a few standard deviations of the channel mean keeps var = E[d^2] - E[d]^2 free of cancellation.  Round 2
 // used row 0 as the shift -- the top-left pixel of image 0, a zero-padded conv border / letterbox region that can sit hundreds of
@@ -1898,18 +1727,16 @@ bn_flat_reduce_k(const float* __restrict__ ws, int lanes, int C8, float* __restr
 // plan of a flat pass: T threads (a multiple of C/8), or 0 when the tensor is too small / not eligible / the workspace is missing
 // In situ (configs[2], B = 128) the flat backward reduce measured 607 samples/s against 612 without it: its dy operand was written by the
 // launch before and the slice form finds more of it in the caches, and the second launch costs what the faster stream gains on the many
-// mid-sized layers.  OFF by default.  The switch is read from the environment ONCE (MMRCA_BN_FLAT=1: both backward-sum and statistics
-// reductions eligible; MMRCA_BN_FLAT_MOMENTS=1: the one-pass moments too) -- BatchNorm launches sit in the launch-bound small-batch
-// path, a getenv per launch does not belong there -- and mmrca_bn_flat_set() lets the tests flip it at run time.
-static int g_bn_flat = ((getenv("MMRCA_BN_FLAT") && atoi(getenv("MMRCA_BN_FLAT")) == 1) ? 1 : 0) |
-                       ((getenv("MMRCA_BN_FLAT_MOMENTS") && atoi(getenv("MMRCA_BN_FLAT_MOMENTS")) == 1) ? 2 : 0);
+// mid-sized layers.  OFF (0) unless mmrca_bn_flat_set() turns it on, which only the tests do: bit 0 makes the backward-sum and
+// statistics reductions eligible, bit 1 the one-pass moments too.
+static int g_bn_flat = 0;
 extern "C" int mmrca_bn_flat_set(int mode) { g_bn_flat = mode & 3; return 0; }
 static bool bn_flat_on() { return (g_bn_flat & 1) != 0; }
-static const int64_t g_bn_flat_threads = getenv("MMRCA_BN_FLAT_THREADS") ? atoll(getenv("MMRCA_BN_FLAT_THREADS")) : 262144;
+static const int64_t BN_FLAT_THREADS = 262144;
 static int64_t bn_flat_threads(int64_t rows, int C, int64_t ld, int dtype, const void* a, const void* b, const void* ws, int64_t ws_bytes) {
   if (!bn_flat_on() || !ws || dtype != MMRCA_BF16 || C % 8 || ld != C || ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)ws)) & 15)) return 0;
   const int64_t C8 = C / 8, nchunk = rows * C8;
-  int64_t T = g_bn_flat_threads;
+  int64_t T = BN_FLAT_THREADS;
   if (T > nchunk / 16) T = nchunk / 16;                 // at least 16 chunks per thread
   if (T * 64 > ws_bytes) T = ws_bytes / 64;
   T = T / C8 * C8;
@@ -2012,7 +1839,6 @@ static void col_grid(int64_t rows, int C, dim3* grid, int64_t* per) {
   *grid = dim3((unsigned)((C + 63) / 64), (unsigned)((rows + *per - 1) / *per));
 }
 
-static const bool g_bn_one_pass = !(getenv("MMRCA_BN_ONE_PASS") && atoi(getenv("MMRCA_BN_ONE_PASS")) == 0);
 /* mean[C], rstd[C] (fp32) of x[rows, C] (two passes: mean, then centred second moment; the bf16 fast path: one pass of shifted sums); momentum > 0 also updates the running
  * statistics (torch semantics).  train == 0: mean / rstd are derived from the running statistics instead. */
 static int bn_stats_impl(const void* x, float* mean, float* rstd, float* running_mean, float* running_var, int64_t rows, int C,
@@ -2038,29 +1864,25 @@ static int bn_stats_impl(const void* x, float* mean, float* rstd, float* running
     (void)hipMemsetAsync(rstd, 0, sizeof(float) * C, st);
   }
   if (dtype == MMRCA_BF16 && C % 8 == 0 && ld % 8 == 0 && (((uintptr_t)x) & 15) == 0) {
-    if (g_bn_one_pass) {
-      // flat form of the moments: measured 94 + 9 us against 100 us for the slice form on a 354 MB tensor -- both sit at the ~4 TB/s that a
-      // READ-ONLY pass reaches on this part (see bn_flat_threads) and the flat one pays a second launch: off unless MMRCA_BN_FLAT_MOMENTS=1
-      const bool flat_moments = (g_bn_flat & 2) != 0;
-      const int64_t T = flat_moments ? bn_flat_threads(rows, C, ld, dtype, x, x, ws, ws_bytes) : 0;
-      if (T) {
-        hipLaunchKernelGGL(col_moment2_flat_k, dim3(blocks_for(T, 256)), dim3(256), 0, st, (const bf16_t*)x, (float*)ws, rows, C / 8, T);
-        bn_flat_reduce((const float*)ws, T, C / 8, mean, rstd, st);
-      } else if (counters) {        // moments + finish in one launch (caller-zeroed tickets, one per 64 channels)
-        hipLaunchKernelGGL(col_moment2_v8_k, grid, dim3(256), 0, st, (const bf16_t*)x, mean, rstd, rows, C, ld, per,
-                           BnFinish{counters, running_mean, running_var, eps, momentum});
-        MMRCA_CHECK_LAUNCH("bn_stats(one pass, fused finish)");
-        return 0;
-      } else
-      hipLaunchKernelGGL(col_moment2_v8_k, grid, dim3(256), 0, st, (const bf16_t*)x, mean, rstd, rows, C, ld, per, BnFinish{nullptr, nullptr, nullptr, 0.f, 0.f});
-      hipLaunchKernelGGL(bn_finish_shifted_k, dim3((C + 255) / 256), dim3(256), 0, st, (const bf16_t*)x, mean, rstd, running_mean, running_var, C,
-                         (float)rows, eps, momentum, rows, ld);
-      MMRCA_CHECK_LAUNCH("bn_stats(one pass)");
+    // flat form of the moments: measured 94 + 9 us against 100 us for the slice form on a 354 MB tensor -- both sit at the ~4 TB/s that a
+    // READ-ONLY pass reaches on this part (see bn_flat_threads) and the flat one pays a second launch: off unless mmrca_bn_flat_set() sets bit 1
+    const bool flat_moments = (g_bn_flat & 2) != 0;
+    const int64_t T = flat_moments ? bn_flat_threads(rows, C, ld, dtype, x, x, ws, ws_bytes) : 0;
+    if (T) {
+      hipLaunchKernelGGL(col_moment2_flat_k, dim3(blocks_for(T, 256)), dim3(256), 0, st, (const bf16_t*)x, (float*)ws, rows, C / 8, T);
+      bn_flat_reduce((const float*)ws, T, C / 8, mean, rstd, st);
+    } else if (counters) {        // moments + finish in one launch (caller-zeroed tickets, one per 64 channels)
+      hipLaunchKernelGGL(col_moment2_v8_k, grid, dim3(256), 0, st, (const bf16_t*)x, mean, rstd, rows, C, ld, per,
+                         BnFinish{counters, running_mean, running_var, eps, momentum});
+      MMRCA_CHECK_LAUNCH("bn_stats(one pass, fused finish)");
       return 0;
-    }
-    hipLaunchKernelGGL((col_moment_v8_k<false>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)nullptr, mean, rows, C, ld, per, 1.0f);
-    hipLaunchKernelGGL((col_moment_v8_k<true>), grid, dim3(256), 0, st, (const bf16_t*)x, (const float*)mean, rstd, rows, C, ld, per, 1.0f / (float)rows);
-  } else
+    } else
+    hipLaunchKernelGGL(col_moment2_v8_k, grid, dim3(256), 0, st, (const bf16_t*)x, mean, rstd, rows, C, ld, per, BnFinish{nullptr, nullptr, nullptr, 0.f, 0.f});
+    hipLaunchKernelGGL(bn_finish_shifted_k, dim3((C + 255) / 256), dim3(256), 0, st, (const bf16_t*)x, mean, rstd, running_mean, running_var, C,
+                       (float)rows, eps, momentum, rows, ld);
+    MMRCA_CHECK_LAUNCH("bn_stats(one pass)");
+    return 0;
+  }
   MMRCA_DISPATCH_DTYPE(dtype, "bn_stats",
     hipLaunchKernelGGL((col_moment_k<T, false>), grid, dim3(256), 0, st, (const T*)x, (const float*)nullptr, mean, rows, C, ld, per, 1.0f);
     hipLaunchKernelGGL((col_moment_k<T, true>), grid, dim3(256), 0, st, (const T*)x, (const float*)mean, rstd, rows, C, ld, per, 1.0f / (float)rows);)
@@ -3062,7 +2884,6 @@ se_mlp_wgrad_k(const T* __restrict__ ds_pre, const T* __restrict__ h, const T* _
   }
 }
 
-static const int g_se_warm = getenv("MMRCA_SE_WARM") ? atoi(getenv("MMRCA_SE_WARM")) : 1;
 extern "C" int mmrca_se_mlp_fwd(const void* pooled, const void* w1, const void* b1, const void* w2, const void* b2, void* h_pre, void* h,
                                 void* s_pre, void* s, int B, int c, int sq, int dtype, void* stream) {
   MMRCA_REQUIRE(pooled && w1 && b1 && w2 && b2 && h_pre && h && s_pre && s, "se_mlp_fwd: null pointer");
@@ -3078,7 +2899,7 @@ extern "C" int mmrca_se_mlp_fwd(const void* pooled, const void* w1, const void* 
   const size_t lds = (size_t)(c + sq) * sizeof(float);
   MMRCA_DISPATCH_DTYPE(dtype, "se_mlp_fwd",
     hipLaunchKernelGGL((se_mlp_fwd_k<T, 16>), dim3(B), dim3(1024), lds, (hipStream_t)stream, (const T*)pooled, (const T*)w1, (const T*)b1, (const T*)w2,
-                       (const T*)b2, (T*)h_pre, (T*)h, (T*)s_pre, (T*)s, c, sq, g_se_warm);)
+                       (const T*)b2, (T*)h_pre, (T*)h, (T*)s_pre, (T*)s, c, sq, 1);)
   MMRCA_CHECK_LAUNCH("se_mlp_fwd");
   return 0;
 }
@@ -3102,7 +2923,7 @@ extern "C" int mmrca_se_mlp_bwd(const void* ds, const void* pooled, const void* 
   MMRCA_DISPATCH_DTYPE(dtype, "se_mlp_bwd",
     // (four waves per sample here: with sixteen the 32-value butterflies of the dh stage outweigh the shorter row walk -- measured)
     hipLaunchKernelGGL((se_mlp_bwd_k<T, 4>), dim3(B), dim3(256), lds, (hipStream_t)stream, (const T*)ds, (const T*)s_pre, (const T*)h_pre,
-                       (const T*)w1, (const T*)b1, (const T*)w2, (const T*)b2, (T*)ds_pre, (T*)dh_pre, (T*)dpool, gb1, gb2, c, sq, g_se_warm);
+                       (const T*)w1, (const T*)b1, (const T*)w2, (const T*)b2, (T*)ds_pre, (T*)dh_pre, (T*)dpool, gb1, gb2, c, sq, 1);
     hipLaunchKernelGGL(se_mlp_wgrad_k<T>, dim3(2 * nb), dim3(256), 0, (hipStream_t)stream, (const T*)ds_pre, (const T*)h, (const T*)dh_pre,
                        (const T*)pooled, gw1, gw2, B, c, sq, nb);)
   MMRCA_CHECK_LAUNCH("se_mlp_bwd");

@@ -68,7 +68,7 @@ int mmrca_sd_rowscale(const float* p, float* out, int n, int B, uint64_t seed, v
 /* timing-only ablation switches for kernel development (0 = normal operation; results are WRONG otherwise) */
 int mmrca_debug_set(int flags);
 /* opt-in flat (streaming) forms of the BatchNorm column reductions: bit 0 = statistics / backward sums, bit 1 = one-pass moments.
- * Initial value: MMRCA_BN_FLAT / MMRCA_BN_FLAT_MOMENTS read once at load; 0 (off) in production.  Needs the `ws` workspace of the
+ * Initial value 0 (off): nothing but this call turns them on, and only the tests make it.  Needs the `ws` workspace of the
  * mmrca_bn_*_ws entry points. */
 int mmrca_bn_flat_set(int mode);
 /* diagnostic: a device buffer of B*H*4 uint64 that the fused ViT attention backward fills with s_memtime stamps of its phases
@@ -241,12 +241,12 @@ int mmrca_dwconv5x5_bwd_ws(const void* dy, const void* x, const void* w, void* d
 int mmrca_bn_stats(const void* x, float* mean, float* rstd, float* running_mean, float* running_var, int64_t rows, int C,
                    int64_t ld, float eps, float momentum, int train, int dtype, void* stream);
 /* the same with a caller workspace (fp32 words, 16-byte aligned; 16 MiB serves every size, NULL = the call above): with
- * MMRCA_BN_FLAT=1 large bf16 tensors take the FLAT streaming reduction -- every wave instruction reads 1 KiB of consecutive addresses,
+ * mmrca_bn_flat_set(1) large bf16 tensors take the FLAT streaming reduction -- every wave instruction reads 1 KiB of consecutive addresses,
  * per-thread partial sums go to the workspace and a second small launch adds them up (3.8-4.3 TB/s against 3.1-3.7 for the
  * slice-per-workgroup form in isolation; no gain inside the conv step, hence opt-in -- csrc/conv.hip) */
 /* mmrca_bn_stats(train = 1) with the finish step (sums -> mean / rstd, running statistics) done by the last workgroup of the reduction
  * instead of a second launch (round 5: one launch less per BatchNorm layer and step -- measured slower in the conv step, the engine
- * does not use it by default; kept, tested, for small tensors outside it).  tickets: ceil(C / 64) int32 words of scratch;
+ * does not use it; kept, tested, for small tensors outside it).  tickets: ceil(C / 64) int32 words of scratch;
  * flags bit 0: the caller zeroed mean, rstd AND tickets.  bf16 with C % 8 == 0; other inputs take the two-launch form. */
 int mmrca_bn_stats_fused(const void* x, float* mean, float* rstd, float* running_mean, float* running_var, int64_t rows, int C,
                          int64_t ld, float eps, float momentum, int dtype, int* tickets, int flags, void* stream);

@@ -678,7 +678,7 @@ def test_tap_major_patch_kernels_are_the_channel_major_ones_permuted(stride):
 
 def test_backbone_bf16_tap_major_equals_channel_major_forward_and_backward():
     """EfficientNetV2-M in bf16: features and every parameter gradient with the dense 3x3 convolutions on tap-major patches
-    (default) against the channel-major path (MMRCA_CONV_TAP_MAJOR=0).  BatchNorm on running statistics: with batch statistics
+    (default) against the channel-major path (conv_engine.TAP_MAJOR = False).  BatchNorm on running statistics: with batch statistics
     over the 12..48 rows this small input leaves in the late stages, bf16 rounding differences between two summation orders are
     amplified to tens of per cent by the normalisation itself (either order is equally far from the fp32 oracle)."""
     from garbage_classification_rca_amd import conv_engine as CE
@@ -714,7 +714,7 @@ def test_backbone_bf16_tap_major_equals_channel_major_forward_and_backward():
 
 @pytest.mark.parametrize("maxrows", [1 << 40, 200])
 def test_weight_gradients_on_the_side_stream_equal_the_one_stream_backward(maxrows):
-    """MMRCA_CONV_SIDE_WGRAD: the 1x1 / implicit-GEMM 3x3 weight gradients launched on a second stream beside the input-gradient chain
+    """conv_engine.SIDE_WGRAD: the 1x1 / implicit-GEMM 3x3 weight gradients launched on a second stream beside the input-gradient chain
     (ConvEncoder._wgrad_stream) -- the same kernels on the same operands, so features are bit-identical and every parameter gradient
     differs from the one-stream backward only by the order in which fp32 atomics land (bound: 1e-4 of the tensor's largest entry; the
     one-stream backward run twice differs by up to ~2e-6).  Three backwards in a row over the same buffers: the second and third find
@@ -803,7 +803,7 @@ def test_batchnorm_forward_with_the_finish_inside_the_apply_pass(R, C, with_res)
 
 def test_backbone_with_the_folded_batchnorm_forward_matches_the_three_launch_form():
     """EfficientNetV2-M, bf16, TRAIN-mode BatchNorm at 96 x 96 (B = 6: the late stages normalise over 54 rows): features, running
-    statistics and every parameter gradient with MMRCA_CONV_BN_FOLD on against off.  Two runs of EITHER form already differ (the sums'
+    statistics and every parameter gradient with conv_engine.BN_FOLD on against off.  Two runs of EITHER form already differ (the sums'
     fp32 atomics land in another order, a bf16 activation flips by one rounding, train-mode BatchNorm over few rows amplifies it), so the
     bound is the distance between two runs of the three-launch form, times three."""
     from garbage_classification_rca_amd import conv_engine as CE
