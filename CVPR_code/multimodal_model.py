@@ -1,2 +1,2 @@
-from garbage_classification_rca_amd.multimodal_model import (MM_RCA, Hierarchical, EffV2MediumAndDistilbertGated, decision,  # noqa: F401
+from garbage_classification_rca_amd.multimodal_model import (MM_RCA, Hierarchical, HierarchicalBimodalFusion, EffV2MediumAndDistilbertGated, decision,  # noqa: F401
                                                             HashingTokenizer)

@@ -21,7 +21,7 @@ import torch
 from .CustomImageTextFolder import CustomImageTextFolder
 from .main_both import DecodeOnly, Transforms, collate_decoded
 from .training import stage_images, trim_caption_columns
-from .multimodal_model import MM_RCA, Hierarchical
+from .multimodal_model import MM_RCA, Hierarchical, HierarchicalBimodalFusion
 from .options import args_parser
 from .training import mode_config_dict
 
@@ -109,7 +109,7 @@ def main(argv=None):
     torch.manual_seed(42)
     np.random.seed(42)
     _batch_size = 16
-    if args.late_fusion not in ("MM_RCA", "hierarchical"):
+    if args.late_fusion not in ("MM_RCA", "hierarchical", "bimodal"):
         print("Wrong late fusion strategy: ", args.late_fusion)
         sys.exit(1)
     from .conv_engine import CONV_MODELS
@@ -120,6 +120,10 @@ def main(argv=None):
     if args.late_fusion == "hierarchical":
         model = Hierarchical(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout, args.num_neurons_FC,
                              args.text_model, _batch_size, args.reverse, **build_kw)
+    elif args.late_fusion == "bimodal":
+        # (the GRUs run over the batch, so the report depends on the batch size and order: 16, in file order)
+        model = HierarchicalBimodalFusion(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout, args.num_neurons_FC,
+                                          args.text_model, _batch_size, args.reverse, **build_kw)
     else:
         model = MM_RCA(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout, args.num_neurons_FC,
                        args.text_model, _batch_size, args.reverse, args.features_only, args.cross_attention_only, **build_kw)

@@ -27,11 +27,12 @@ void* mmrca_seed_epoch_addr_attention_f32();
 void* mmrca_seed_epoch_addr_attention_mfma();
 void* mmrca_seed_epoch_addr_attention_ref();
 void* mmrca_seed_epoch_addr_classifier();
+void* mmrca_seed_epoch_addr_gru();
 void* mmrca_seed_epoch_addr_head();
 void* mmrca_seed_epoch_addr_hier_head();
 void* mmrca_seed_epoch_addr_rowops();
 }
-#define MMRCA_N_EPOCH_COPIES 9
+#define MMRCA_N_EPOCH_COPIES 10
 struct EpochCopies { unsigned long long* p[MMRCA_N_EPOCH_COPIES]; };
 
 __global__ void seed_epoch_set_k(EpochCopies c, const unsigned long long* __restrict__ src, unsigned long long value) {
@@ -55,7 +56,8 @@ extern "C" int mmrca_seed_epoch_set(const uint64_t* device_value, uint64_t value
     if (!ready[dev]) {
       void* a[MMRCA_N_EPOCH_COPIES] = {mmrca_seed_epoch_addr_attention_cls(), mmrca_seed_epoch_addr_attention_cross(), mmrca_seed_epoch_addr_attention_f32(),
                                        mmrca_seed_epoch_addr_attention_mfma(), mmrca_seed_epoch_addr_attention_ref(), mmrca_seed_epoch_addr_head(),
-                                       mmrca_seed_epoch_addr_rowops(), mmrca_seed_epoch_addr_classifier(), mmrca_seed_epoch_addr_hier_head()};
+                                       mmrca_seed_epoch_addr_rowops(), mmrca_seed_epoch_addr_classifier(), mmrca_seed_epoch_addr_hier_head(),
+                                       mmrca_seed_epoch_addr_gru()};
       for (int i = 0; i < MMRCA_N_EPOCH_COPIES; ++i) {
         if (!a[i]) return mmrca_fail(-10, "seed_epoch_set: hipGetSymbolAddress failed for copy %d on device %d", i, dev);
         copies[dev].p[i] = (unsigned long long*)a[i];

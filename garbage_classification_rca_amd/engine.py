@@ -186,7 +186,7 @@ class MMRCAEngine:
         ents = [("text_model." + k, s) for k, s in S.text_params(self.ts)]
         vis_ents = S.vision_params(self.vs) if self.vs is not None else self.conv.param_entries()
         ents += [("image_model." + k, s) for k, s in vis_ents]
-        self.head_keys = S.head_used_params(self.d_img, self.d_txt, n_classes, mode == 1, mode == 2)
+        self.head_keys = self._head_entries()
         ents += self.head_keys
         self.arena = Arena(ents, self.device, with_lp=(dtype == torch.bfloat16 or self.x3), with_lo=self.x3)
         self.param_keys = [k for k, _ in ents]
@@ -267,6 +267,11 @@ class MMRCAEngine:
             self.grad_sync.span_ready(lo, hi, flush)
 
     # ------------------------------------------------------------------ parameters
+    def _head_entries(self):
+        """(key, shape) of the head's parameters, in arena order (a subclass with another head over the same encoders overrides this and
+        ``_head_struct``)"""
+        return S.head_used_params(self.d_img, self.d_txt, self.n_classes, self.mode == 1, self.mode == 2)
+
     def _head_struct(self, which) -> L.HeadPtrs:
         names = {"sai": "self_attention_image", "sat": "self_attention_text", "c1": "cross_attention_1", "c2": "cross_attention_2"}
         leaf = {"wq": "W_query.weight", "bq": "W_query.bias", "wk": "W_key.weight", "bk": "W_key.bias",

@@ -141,6 +141,13 @@ _SIGS = {
     "mmrca_hier_norm_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _u64, _u64, _vp],
     "mmrca_hier_linear_relu_fwd": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
     "mmrca_hier_linear_relu_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
+    "mmrca_gru_linear_fwd": [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "mmrca_gru_linear_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "mmrca_gru_fwd": [_i32] + [_vp] * 6 + [_i32, _i32, _vp],
+    "mmrca_gru_bwd": [_i32] + [_vp] * 9 + [_i32, _i32, _vp],
+    "mmrca_hadamard_fwd": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "mmrca_hadamard_bwd": [_vp, _i32] * 5 + [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp],
+    "mmrca_dropout_f32": [_vp, _i32, _vp, _i32, _i32, _i32, _f32, _u64, _vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["mmrca_last_error", "mmrca_version", "mmrca_debug_set", "mmrca_bn_flat_set", "mmrca_debug_attn_stamps", "mmrca_gemm_splitk_workspace_bytes", "mmrca_gemm_streamk_workspace_bytes",
                                   "mmrca_head_bwd_workspace_bytes", "mmrca_conv3x3_stat_slots", "mmrca_gemm_bnstats_slots",
@@ -659,6 +666,77 @@ def hier_linear_relu_bwd(dY, lddy, Y, ldy, X, ldx, W, dW, db, dX, lddx, ws, B, N
         _check(load().mmrca_hier_linear_relu_bwd(ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, ptr(ws),
                                                  0 if ws is None else ws.numel() * ws.element_size(), B, N, K, stream_ptr()),
                "mmrca_hier_linear_relu_bwd")
+
+
+# ---- head of the bimodal GRU late-fusion model (csrc/gru.hip) ---------------------------------------------------------------
+def gru_linear_fwd(X, ldx, W, b, Y, ldy, B, N, K, relu=False):
+    """Y [B, N] = X W^T + b (then ReLU); fp32, row pitches in elements"""
+    _dev(X, "gru_linear X")
+    with _Bracket("gru_linear_fwd", (B, N, K)):
+        _check(load().mmrca_gru_linear_fwd(ptr(X), ldx, ptr(W), ptr(b), ptr(Y), ldy, B, N, K, int(bool(relu)), stream_ptr()), "mmrca_gru_linear_fwd")
+
+
+def gru_linear_bwd(dY, lddy, Y, ldy, X, ldx, W, dW, db, dX, lddx, B, N, K):
+    """dW += dZ^T X, db += colsum(dZ), dX = dZ W with dZ = dY (* (Y > 0) when Y is given); dW / db / dX are each optional"""
+    _dev(dY, "gru_linear dY")
+    with _Bracket("gru_linear_bwd", (B, N, K)):
+        _check(load().mmrca_gru_linear_bwd(ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, B, N, K, stream_ptr()),
+               "mmrca_gru_linear_bwd")
+
+
+def _ptr_table(tensors, name):
+    for t in tensors:
+        _dev(t, name)
+        if t.dtype != torch.float32:
+            raise MmrcaError(f"{name}: fp32 tensors only, got {t.dtype}")
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def gru_fwd(gi, whh, bhh, hseq, gates, hn, T, H):
+    """the recurrent chain of len(gi) (1 or 2) GRUs of the same T and H, one launch per step; every argument is a list of tensors.
+    hseq [T + 1, H]: row 0 = h_{-1} (the caller's), rows 1 .. T are written"""
+    n = len(gi)
+    if not all(len(v) == n for v in (whh, bhh, hseq, gates, hn)):
+        raise MmrcaError("gru_fwd: every argument lists one tensor per GRU")
+    for g, s, a, h in zip(gi, hseq, gates, hn):
+        if g.numel() < T * 3 * H or a.numel() < T * 3 * H or s.numel() < (T + 1) * H or h.numel() < T * H:
+            raise MmrcaError(f"gru_fwd: a buffer is smaller than T={T}, H={H} need")
+    with _Bracket("gru_fwd", (n, T, H)):
+        _check(load().mmrca_gru_fwd(n, *[_ptr_table(v, "gru_fwd") for v in (gi, whh, bhh, hseq, gates, hn)], T, H, stream_ptr()), "mmrca_gru_fwd")
+
+
+def gru_bwd(whh, hseq, gates, hn, dout, lddout, carry, dgi, dgh, T, H):
+    """the backward chain: writes dgi / dgh [T, 3H] (the gradients at W_ih x + b_ih and at W_hh h + b_hh); carry [T, H] is scratch"""
+    n = len(whh)
+    if not all(len(v) == n for v in (hseq, gates, hn, dout, lddout, carry, dgi, dgh)):
+        raise MmrcaError("gru_bwd: every argument lists one entry per GRU")
+    for s, a, h, d, ld, c, gi_, gh_ in zip(hseq, gates, hn, dout, lddout, carry, dgi, dgh):
+        if (a.numel() < T * 3 * H or gi_.numel() < T * 3 * H or gh_.numel() < T * 3 * H or s.numel() < (T + 1) * H or h.numel() < T * H
+                or c.numel() < T * H or ld < H):
+            raise MmrcaError(f"gru_bwd: a buffer is smaller than T={T}, H={H} need")
+    lds = (C.c_int * n)(*[int(v) for v in lddout])
+    with _Bracket("gru_bwd", (n, T, H)):
+        _check(load().mmrca_gru_bwd(n, *[_ptr_table(v, "gru_bwd") for v in (whh, hseq, gates, hn, dout)], lds,
+                                    *[_ptr_table(v, "gru_bwd") for v in (carry, dgi, dgh)], T, H, stream_ptr()), "mmrca_gru_bwd")
+
+
+def hadamard_fwd(a, lda, x2, ldb, k1, k2, bias, out, ldo, B, Cc):
+    """out = tanh(a * k1 + x2 * k2 + bias) over [B, Cc]"""
+    _dev(a, "hadamard a")
+    _check(load().mmrca_hadamard_fwd(ptr(a), lda, ptr(x2), ldb, ptr(k1), ptr(k2), ptr(bias), ptr(out), ldo, B, Cc, stream_ptr()), "mmrca_hadamard_fwd")
+
+
+def hadamard_bwd(d1, ld1, d2, ld2, a, lda, x2, ldb, out, ldo, k1, k2, da, ldda, db, lddb, dk1, dk2, dbias, B, Cc):
+    """d = (d1 + d2) (1 - out^2): da = d k1, db = d k2; dk1 / dk2 / dbias accumulate.  d2 may be None"""
+    _dev(d1, "hadamard d1")
+    _check(load().mmrca_hadamard_bwd(ptr(d1), ld1, ptr(d2), ld2, ptr(a), lda, ptr(x2), ldb, ptr(out), ldo, ptr(k1), ptr(k2), ptr(da), ldda,
+                                     ptr(db), lddb, ptr(dk1), ptr(dk2), ptr(dbias), B, Cc, stream_ptr()), "mmrca_hadamard_bwd")
+
+
+def dropout_f32(x, ldx, y, ldy, B, Cc, drop_p, seed):
+    """y = x * keep / (1 - drop_p) with the counter-based mask of (seed, b * Cc + c); the backward is the same call on the gradient"""
+    _dev(x, "dropout x")
+    _check(load().mmrca_dropout_f32(ptr(x), ldx, ptr(y), ldy, B, Cc, float(drop_p), _u64v(seed), stream_ptr()), "mmrca_dropout_f32")
 
 
 _seed_epoch = 0                  # host view of the device-side mask epoch (0 = eager launches draw the seeds they are given)

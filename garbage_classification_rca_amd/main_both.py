@@ -10,7 +10,7 @@ everything trainable for ``--ft_epochs`` at lr/``--fraction_lr``, main_both.py:5
 the fine-tuning phase only, best-validation checkpointing with the reference's file-name pattern, wandb keys (wandb is
 optional here: it needs network).  Replaced: ``nn.DataParallel`` -> sharded sampler + overlapped RCCL gradient
 all-reduce; ``torch.optim`` -> fused flat-arena optimizers (same update rules).
-``--late_fusion=MM_RCA`` and ``--late_fusion=hierarchical`` are built (SURVEY.md header); every other value exits as in the reference.
+``--late_fusion=MM_RCA``, ``hierarchical`` and ``bimodal`` are built (SURVEY.md header); every other value exits as in the reference.
 """
 from __future__ import annotations
 
@@ -25,7 +25,7 @@ import torch
 
 from . import distributed as D
 from .CustomImageTextFolder import CustomImageTextFolder, SyntheticImageTextDataset
-from .multimodal_model import MM_RCA, Hierarchical
+from .multimodal_model import MM_RCA, Hierarchical, HierarchicalBimodalFusion
 from .optim import FlatAdamW, FlatSGD
 from .options import args_parser
 from .training import (calculate_set_accuracy, get_class_weights_from_counts, mode_config_dict, run_one_epoch)
@@ -165,6 +165,12 @@ def main(argv=None):
         # the reference's eight positionals (main_both.py:319-327); a configuration the three linears do not fit raises here
         global_model = Hierarchical(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout,
                                     args.num_neurons_FC, args.text_model, _batch_size, args.reverse, **build_kw)
+    elif args.late_fusion == "bimodal":
+        # the reference overrides both batch sizes for this model (main_both.py:329-330).  Its GRUs run over the batch, so the batch
+        # size is the sequence length; under data parallelism every rank runs the recurrence over its own local batch.
+        _batch_size, _batch_size_FT = 32, 4
+        global_model = HierarchicalBimodalFusion(_num_classes, args.model_dropout, args.image_text_dropout, args.image_prob_dropout,
+                                                 args.num_neurons_FC, args.text_model, _batch_size, args.reverse, **build_kw)
     else:
         print("Wrong late fusion strategy: ", args.late_fusion)       # main_both.py:341-343
         sys.exit(1)

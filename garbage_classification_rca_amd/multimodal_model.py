@@ -1,4 +1,5 @@
-"""Drop-in ``MM_RCA`` and ``Hierarchical`` modules (mirrors CVPR_code/multimodal_model.py:156-328, 636-728 of the reference).
+"""Drop-in ``MM_RCA``, ``Hierarchical`` and ``HierarchicalBimodalFusion`` modules (mirrors CVPR_code/multimodal_model.py:156-328, 636-888
+of the reference).
 
 Same constructor argument order as the reference's call at main_both.py:306-317, same
 ``forward(_input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False)``, same
@@ -282,7 +283,7 @@ class EffV2MediumAndDistilbertGated(torch.nn.Module):
         return self
 
     def forward(self, _input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False):
-        raise NotImplementedError("only the MM_RCA and Hierarchical forwards are built (the other fusion forwards have no launcher in the reference)")
+        raise NotImplementedError("only the MM_RCA, Hierarchical and HierarchicalBimodalFusion forwards are built (the other fusion forwards cannot run in the reference either)")
 
     def _engine_forward(self, _input_ids, _attention_mask, _images, eval, remove_image, remove_text):
         """modality dropout on the host, then the whole model as one autograd node over the engine"""
@@ -327,6 +328,44 @@ class Hierarchical(EffV2MediumAndDistilbertGated):
     def _make_engine(self, text_model_name, image_model_name, n_classes, reverse, mode, dtype, device):
         from .hierarchical_engine import HierarchicalEngine
         return HierarchicalEngine(text_model_name, image_model_name, n_classes, dtype, device, image_size=self.image_size)
+
+    def _unused_param_entries(self, n_classes, num_neurons_fc, batch_size):
+        return (S.head_used_params(self.engine.d_img, self.engine.d_txt, n_classes, False, False)
+                + S.head_unused_params(self.engine.d_img, self.engine.d_txt, n_classes, num_neurons_fc, batch_size, False, False))
+
+    def forward(self, _input_ids, _attention_mask, _images, eval=False, remove_image=False, remove_text=False):
+        return self._engine_forward(_input_ids, _attention_mask, _images, eval, remove_image, remove_text)
+
+
+class HierarchicalBimodalFusion(EffV2MediumAndDistilbertGated):
+    """multimodal_model.py:835-888: the L2-normalised class token and pooled image feature, each projected to 400, each through its own
+    context GRU, fused by tanh(ctx_text * kernel1 + ctx_audio * kernel2 + bias), a 500-wide GRU over the fused rows, then
+    concat_fc + ReLU and the 4-way classifier (bimodal_engine.BimodalEngine).
+
+    The GRUs run over the BATCH: each receives a 2-D tensor, which torch reads as one unbatched sequence, so row b of the batch is time
+    step b and sample b's logits depend on samples 0 .. b - 1.  That is the reference's behaviour, reproduced here.  The logits are 4
+    wide whatever ``n_classes`` is (``num_classes = 4`` is hard-coded, :305); dropout1 / dropout2 are fixed at 0.86 in train mode and
+    ``drop_ratio`` (--model_dropout) has no effect on this forward.
+
+    Takes the eight positionals of the reference's launch (main_both.py:332-340; its constructor wants ten, so the reference's own call
+    raises TypeError) plus the build's keyword arguments, any backbone pair and image size MM_RCA takes.  ``state_dict()`` has the keys and
+    shapes of ``MM_RCA(..., reverse, False, False)``: the RCA blocks, final_with_everything and the hierarchical linears are the
+    present-but-unused keys here, the GRUs, fusion, concat_fc, modality_*_to_dim and classifier the arena parameters, so checkpoints
+    interchange in both directions."""
+
+    def __init__(self, n_classes, drop_ratio, image_or_text_dropout_chance, img_prob_dropout, num_neurons_fc, text_model_name, batch_size,
+                 reverse, image_model_name: str = "eff_v2_medium", dtype="bf16x3f", device="cuda", init_seed: int = 0,
+                 build_unused_parameters: bool = True, image_size: Optional[int] = None):
+        super().__init__(n_classes, drop_ratio, image_or_text_dropout_chance, img_prob_dropout, num_neurons_fc, text_model_name, batch_size,
+                         reverse, False, False, image_model_name=image_model_name, dtype=dtype, device=device, init_seed=init_seed,
+                         build_unused_parameters=build_unused_parameters, image_size=image_size)
+        from .bimodal_engine import BIMODAL_DROPOUT
+        self.model_dropout = float(drop_ratio)         # (self.drop of the reference: built, never called in this forward)
+        self.drop_ratio = BIMODAL_DROPOUT              # what the train step hands the engine: dropout1 / dropout2
+
+    def _make_engine(self, text_model_name, image_model_name, n_classes, reverse, mode, dtype, device):
+        from .bimodal_engine import BimodalEngine
+        return BimodalEngine(text_model_name, image_model_name, n_classes, dtype, device, image_size=self.image_size)
 
     def _unused_param_entries(self, n_classes, num_neurons_fc, batch_size):
         return (S.head_used_params(self.engine.d_img, self.engine.d_txt, n_classes, False, False)

@@ -34,7 +34,7 @@ REFERENCE_FLAGS = [
     ("base_path", _STR, r"D:\Mestrado\ENSF_619_02_Final_project_jose_cazarin\BEST_MODELS_CVPR_2025", "accepted for CLI compatibility; unused here as in the reference (paths are relative to the working directory)"),
     ("calculate_dataset_stats", _BOOL, False, "recompute the normalisation statistics"),
     ("prob_aug", _FLOAT, 0.6, "probability of each image augmentation"),
-    ("late_fusion", _STR, "gated", "fusion head (MM_RCA and hierarchical are the ones built here)"),
+    ("late_fusion", _STR, "gated", "fusion head (MM_RCA, hierarchical and bimodal are the ones built here)"),
     ("label_smoothing", _FLOAT, 0.0, "label smoothing of the loss"),
     ("name", _STR, None, "free-text run description"),
     ("reverse", _BOOL, False, "reverse cross-attention, (1 - A) / (n - 1)"),

@@ -526,6 +526,41 @@ int mmrca_hier_linear_relu_fwd(const float* X, int ldx, const float* W, const fl
 int mmrca_hier_linear_relu_bwd(const float* dY, int lddy, const float* Y, int ldy, const float* X, int ldx, const float* W,
                                float* dW, float* db, float* dX, int lddx, float* ws, int64_t ws_bytes, int B, int N, int K, void* stream);
 
+/* K1d. head of the bimodal GRU late-fusion model (multimodal_model.HierarchicalBimodalFusion; csrc/gru.hip).  fp32 arithmetic and
+ * storage; no atomics, every sum in a fixed order (bitwise reproducible); weight gradients ACCUMULATE.
+ *
+ * gru_linear: Y [B, N] (row pitch ldy) = X W^T + b (relu != 0: followed by ReLU), X [B, K] (row pitch ldx), W [N, K], b optional; any
+ * N, K in [1, 65536] (16-byte loads when K % 4 == 0, the pitch % 4 == 0 and the pointers are 16-byte aligned, else single floats).
+ * bwd: dZ = dY (* (Y > 0) when Y is given); dW (optional) += dZ^T X and db (optional) += column sums of dZ, samples in order;
+ * dX (optional, row pitch lddx) = dZ W. */
+int mmrca_gru_linear_fwd(const float* X, int ldx, const float* W, const float* b, float* Y, int ldy, int B, int N, int K, int relu,
+                         void* stream);
+int mmrca_gru_linear_bwd(const float* dY, int lddy, const float* Y, int ldy, const float* X, int ldx, const float* W, float* dW, float* db,
+                         float* dX, int lddx, int B, int N, int K, void* stream);
+/* gru: the recurrent chain of one layer in torch's cell and layout (weight_hh [3H, H], bias_hh [3H], gate rows r | z | n), ONE launch
+ * per time step; `ngru` = 1 or 2 independent GRUs of the same T and H share every launch.  Every argument is a HOST table of ngru
+ * pointers.  gi [T, 3H] = W_ih x_t + b_ih for all t (gru_linear_fwd).  hseq [T + 1, H]: row 0 = h_{-1}, set by the caller (zeros for
+ * an unbatched torch GRU without h0), row t + 1 = h_t is written.  Saved for the backward: gates [T, 3H] = r | z | n and
+ * hn [T, H] = W_hn h + b_hn.  H % 4 == 0, 4 <= H <= 512; weight_hh and hseq 16-byte aligned.
+ * bwd: dout [T, H] (row pitch lddout[i]) = the gradient at rows 1 .. T of hseq.  Writes dgi [T, 3H] = the gradient at gi (dW_ih +=
+ * dgi^T x, db_ih += its column sums, dx = dgi W_ih) and dgh [T, 3H] = the gradient at W_hh h + b_hh (dW_hh += dgh^T hseq[0 .. T - 1],
+ * db_hh += its column sums): the caller forms those products once over all T (gru_linear_bwd).  carry [T, H] is scratch. */
+int mmrca_gru_fwd(int ngru, const float* const* gi, const float* const* whh, const float* const* bhh, float* const* hseq,
+                  float* const* gates, float* const* hn, int T, int H, void* stream);
+int mmrca_gru_bwd(int ngru, const float* const* whh, const float* const* hseq, const float* const* gates, const float* const* hn,
+                  const float* const* dout, const int* lddout, float* const* carry, float* const* dgi, float* const* dgh, int T, int H,
+                  void* stream);
+/* hadamard: out[b, c] = tanh(a[b, c] k1[c] + x2[b, c] k2[c] + bias[c]) over [B, C] with row pitches.  bwd: d = (d1 + d2) (1 - out^2)
+ * (d2 optional: a second gradient arriving at out); da = d k1, db = d k2, dk1 += sum_b d a, dk2 += sum_b d x2, dbias += sum_b d. */
+int mmrca_hadamard_fwd(const float* a, int lda, const float* x2, int ldb, const float* k1, const float* k2, const float* bias, float* out,
+                       int ldo, int B, int C, void* stream);
+int mmrca_hadamard_bwd(const float* d1, int ld1, const float* d2, int ld2, const float* a, int lda, const float* x2, int ldb,
+                       const float* out, int ldo, const float* k1, const float* k2, float* da, int ldda, float* db, int lddb, float* dk1,
+                       float* dk2, float* dbias, int B, int C, void* stream);
+/* dropout: y[b, c] = x[b, c] * keep / (1 - drop_p), keep = the counter hash of (seed + mask epoch, b * C + c) >= drop_p
+ * (mmrca_seed_epoch_set applies).  The backward is the same call on the gradient with the forward's seed.  y may be x. */
+int mmrca_dropout_f32(const float* x, int ldx, float* y, int ldy, int B, int C, float drop_p, uint64_t seed, void* stream);
+
 /* K6. weighted, label-smoothed cross entropy (torch.nn.CrossEntropyLoss as built at main_both.py:87-93), mean
  * reduction with the weighted denominator.  loss: fp32[1]; dlogits (optional): fp32 [B,C] scaled by grad_scale. */
 int mmrca_xent_fwd_bwd(const float* logits, const int32_t* labels, const float* class_w, float smoothing,
