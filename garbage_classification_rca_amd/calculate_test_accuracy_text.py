@@ -14,11 +14,11 @@ import numpy as np
 import torch
 
 from .CustomImageTextFolder import CustomImageTextFolder
-from .classifiers import TEXT_FACTORIES
+from .classifiers import build_text_classifier
 from .options import args_parser
 from .single_modality import calculate_test_accuracy, invalid_model, no_image, write_report
 
-BATCHES = {"distilbert": 128, "roberta": 128, "bert": 128}
+BATCHES = {"distilbert": 128, "roberta": 128, "bert": 128, "mobile_bert": 18}     # (:155-177)
 
 
 def main(argv=None):
@@ -37,7 +37,7 @@ def main(argv=None):
     _batch_size = BATCHES[args.text_model]
     print("Text Model: {}".format(args.text_model))
     dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}.get(args.dtype, args.dtype)
-    model = TEXT_FACTORIES[args.text_model](4, args.model_dropout, dtype=dtype, device=device)
+    model = build_text_classifier(args.text_model, 4, args.model_dropout, dtype, device)
     model.load_state_dict(torch.load(args.model_path, map_location="cpu"))
     model.eval()
     max_len = args.tokens_max_len or model.get_max_token_size()

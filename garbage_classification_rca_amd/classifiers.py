@@ -1,5 +1,6 @@
 """Single-modality classifiers on the HIP path: drop-ins for the reference's image models (models.py: ``VisionB16``, ``VisionL16``,
-``EffNetV2_M``, ``EffNetV2_L``, ``ShuffleNetV2``) and text models (CVPR_code/text_models.py: ``DistilBert``, ``Bert``, ``Roberta``).
+``EffNetV2_M``, ``EffNetV2_L``, ``ShuffleNetV2``) and text models (CVPR_code/text_models.py: ``DistilBert``, ``Bert``, ``Roberta``,
+``MobileBert``).
 
 Each factory returns a module whose arithmetic runs in :class:`~garbage_classification_rca_amd.classifier_engine.ClassifierEngine`
 (one backbone + ``mmrca_linear_cls_*``).  ``forward(images)`` / ``forward(_input_ids, _attention_mask)`` returns fp32 logits through one
@@ -10,7 +11,9 @@ autograd node (``loss.backward()`` runs the HIP backward and accumulates into ``
 * EfficientNetV2: ``features.0`` .. ``features.8`` (BatchNorm buffers included), head ``classifier.1.*``;
 * ShuffleNetV2: ``conv1``, ``stage2`` .. ``stage4``, ``conv5``, head ``fc.*``;
 * MobileNetV3-Large: ``features.0`` .. ``features.16`` and ``classifier.0`` (BatchNorm buffers included), head ``classifier.3.*``;
-* text: ``model.<transformers keys>`` (RoBERTa's unused ``model.pooler`` included, as ``RobertaModel`` builds it), head ``out.*``.
+* text: ``model.<transformers keys>`` (RoBERTa's unused ``model.pooler`` included, as ``RobertaModel`` builds it), head ``out.*``;
+* MobileBERT: ``model.mobilebert.*`` and the head ``model.classifier.*`` -- ``MobileBertForSequenceClassification``'s own keys under
+  the reference's attribute ``model`` (mobilebert_engine.py; fp32 or bf16, no dropout in front of the head).
 
 What the head sees (models.py / text_models.py): ViT the ``encoder.ln`` output of the class token, no dropout (torchvision's ``heads`` is
 a Linear alone); EfficientNetV2 the average-pooled ``features.8`` output behind ``classifier[0] = Dropout(0.3 / 0.4)``; ShuffleNetV2 the
@@ -38,13 +41,15 @@ from .multimodal_model import HashingTokenizer, ParamTree, _EngineFunction
 # (mobilenet_v3_large: classifier = Sequential(Linear(960, 1280), Hardswish, Dropout(0.2), Linear) -- the first two are the backbone's)
 IMAGE_HEAD_DROPOUT = {"transformer_B16": 0.0, "transformer_L16": 0.0, "eff_v2_medium": 0.3, "eff_v2_large": 0.4, "shuffle_net": 0.0, "mb": 0.2}
 HEAD_NAME = {"transformer_B16": "heads.head", "transformer_L16": "heads.head", "eff_v2_medium": "classifier.1",
-             "eff_v2_large": "classifier.1", "shuffle_net": "fc", "mb": "classifier.3", "distilbert": "out", "bert": "out", "roberta": "out"}
+             "eff_v2_large": "classifier.1", "shuffle_net": "fc", "mb": "classifier.3", "distilbert": "out", "bert": "out", "roberta": "out",
+             "mobile_bert": "model.classifier"}
 DEFAULT_IMAGE_SIZE = {"eff_v2_medium": 480, "eff_v2_large": 480, "mb": 320}      # (main_image.py: the reference's input sizes; others 224)
 # the EfficientNetV2 extractor's attribute names (conv_engine.py, the MM_RCA checkpoint names) -> torchvision's `features` index
 _EFF_FEATURES = {"stem.0": "features.0", "stem.1": "features.1", "stage1": "features.2", "stage2": "features.3", "stage3": "features.4",
                  "stage4": "features.5", "stage5": "features.6", "stage6": "features.7", "final_conv": "features.8"}
 _EFF_RE = re.compile(r"^(stem\.[01]|stage\d|final_conv)\.")
-TOKENIZER_NAMES = {"bert": "bert-base-uncased", "distilbert": "distilbert-base-uncased", "roberta": "roberta-base"}
+TOKENIZER_NAMES = {"bert": "bert-base-uncased", "distilbert": "distilbert-base-uncased", "roberta": "roberta-base",
+                   "mobile_bert": "google/mobilebert-uncased"}
 
 
 def external_name(backbone: str, key: str) -> str:
@@ -76,7 +81,7 @@ class SingleBackboneClassifier(torch.nn.Module):
             self.image_size = S.VISION_SPECS[backbone].image
         else:
             self.image_size = int(image_size or DEFAULT_IMAGE_SIZE.get(backbone, 224))
-        self.engine = ClassifierEngine(backbone, n_classes, dtype, device, image_size=self.image_size)
+        self.engine = self._make_engine(backbone, n_classes, dtype, device)
         self.engine.init_parameters(init_seed)
         self.kind, self.n_classes = self.engine.kind, n_classes
         self.drop_ratio = float(head_dropout)
@@ -105,6 +110,9 @@ class SingleBackboneClassifier(torch.nn.Module):
                 self.model.pooler.dense.weight.requires_grad = False
                 self.model.pooler.dense.bias.requires_grad = False
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
+
+    def _make_engine(self, backbone, n_classes, dtype, device):
+        return ClassifierEngine(backbone, n_classes, dtype, device, image_size=self.image_size)
 
     def _add(self, dotted, t, param):
         node = self
@@ -248,6 +256,35 @@ def Roberta(n_classes, drop_ratio, **kw):
     return TextClassifier("roberta", n_classes, drop_ratio, True, **kw)
 
 
+class MobileBertClassifier(TextClassifier):
+    """the same module over :class:`~garbage_classification_rca_amd.mobilebert_engine.MobileBertEngine`"""
+
+    def __init__(self, *a, spec=None, **kw):
+        object.__setattr__(self, "_spec", spec)         # (tests build shallow models: a MobileBertSpec with fewer layers)
+        super().__init__(*a, **kw)
+
+    def _make_engine(self, backbone, n_classes, dtype, device):
+        from .mobilebert_engine import MOBILEBERT, MobileBertEngine
+        return MobileBertEngine(n_classes, dtype, device, spec=self._spec or MOBILEBERT)
+
+
+def MobileBERT(n_classes, dtype="fp32", **kw):
+    """text_models.py MobileBert: MobileBertForSequenceClassification (frozen) with classifier = Linear(512, n_classes), trainable; no
+    dropout argument (the model's classifier dropout is 0).  dtype: "fp32" (default, the compliant mode) or "bf16"."""
+    return MobileBertClassifier("mobile_bert", n_classes, 0.0, True, dtype=dtype, **kw)
+
+
 IMAGE_FACTORIES = {"transformer_B16": VisionB16, "transformer_L16": VisionL16, "eff_v2_medium": EffNetV2_M, "eff_v2_large": EffNetV2_L,
                    "shuffle_net": ShuffleNetV2, "mb": MBNetLarge}
-TEXT_FACTORIES = {"distilbert": DistilBert, "bert": Bert, "roberta": Roberta}
+TEXT_FACTORIES = {"distilbert": DistilBert, "bert": Bert, "roberta": Roberta, "mobile_bert": MobileBERT}
+
+
+def build_text_classifier(name, n_classes, model_dropout, dtype, device):
+    """what main_text.py / calculate_test_accuracy_text.py construct for --text_model=name: the reference's call per model
+    (``MobileBERT(n)`` takes no dropout).  MobileBERT has no split-bf16 mode: under the scripts' default --dtype it runs in fp32."""
+    if name == "mobile_bert":
+        if isinstance(dtype, str) and dtype.lower() not in ("fp32", "f32", "bf16"):
+            print("mobile_bert: --dtype {} is not built for this model; using fp32 (pass --dtype bf16 for the bf16 mode)".format(dtype))
+            dtype = "fp32"
+        return MobileBERT(n_classes, dtype=dtype, device=device)
+    return TEXT_FACTORIES[name](n_classes, model_dropout, dtype=dtype, device=device)

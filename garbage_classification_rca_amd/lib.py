@@ -148,10 +148,14 @@ _SIGS = {
     "mmrca_hadamard_fwd": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     "mmrca_hadamard_bwd": [_vp, _i32] * 5 + [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp],
     "mmrca_dropout_f32": [_vp, _i32, _vp, _i32, _i32, _i32, _f32, _u64, _vp],
+    "mmrca_nonorm_fwd": [_vp] * 6 + [_i64, _i32] + [_i64] * 4 + [_i32, _vp],
+    "mmrca_nonorm_bwd": [_vp] * 9 + [_i64, _i64, _i32] + [_i64] * 4 + [_i32, _vp],
+    "mmrca_trigram_embed_fwd": [_vp] * 4 + [_i64] + [_i32] * 5 + [_vp],
+    "mmrca_trigram_embed_bwd": [_vp] * 4 + [_i64] + [_i32] * 6 + [_vp],
 }
 EXPORTS = sorted(list(_SIGS) + ["mmrca_last_error", "mmrca_version", "mmrca_debug_set", "mmrca_bn_flat_set", "mmrca_debug_attn_stamps", "mmrca_gemm_splitk_workspace_bytes", "mmrca_gemm_streamk_workspace_bytes",
                                   "mmrca_head_bwd_workspace_bytes", "mmrca_conv3x3_stat_slots", "mmrca_gemm_bnstats_slots",
-                                  "mmrca_hier_linear_workspace_bytes"])
+                                  "mmrca_hier_linear_workspace_bytes", "mmrca_nonorm_bwd_workspace_bytes"])
 
 
 def load(build_if_missing: bool = False):
@@ -175,6 +179,8 @@ def load(build_if_missing: bool = False):
     lib.mmrca_gemm_streamk_workspace_bytes.restype = _i64
     lib.mmrca_hier_linear_workspace_bytes.argtypes = [_i32, _i32, _i32]
     lib.mmrca_hier_linear_workspace_bytes.restype = _i64
+    lib.mmrca_nonorm_bwd_workspace_bytes.argtypes = [_i64, _i32]
+    lib.mmrca_nonorm_bwd_workspace_bytes.restype = _i64
     lib.mmrca_conv3x3_stat_slots.argtypes = [_i32, _i32, _i32]
     lib.mmrca_conv3x3_stat_slots.restype = _i64
     lib.mmrca_last_error.restype = C.c_char_p
@@ -1063,3 +1069,36 @@ def channel_deinterleave2(dout, d_even, ld_even, d_odd, rows, bf, dtype):
 
 def channel_gather(inp, cmap, out, rows, Cin, Cout, ld_out, col0, dtype):
     _c("mmrca_channel_gather", ptr(inp), ptr(cmap), ptr(out), rows, Cin, Cout, ld_out, col0, dtype)
+
+
+# ---- MobileBERT row operators (csrc/mobilebert.hip) -----------------------------------------------------------------------------
+def nonorm_fwd(x, res, gamma, beta, sum_out, y, rows, D, ld_x, ld_res, ld_sum, ld_y, dtype):
+    """s = x (+ res), y = s * gamma + beta on [rows, D]; sum_out (optional, may be x) receives s"""
+    _dev(x, "nonorm_fwd x")
+    _check(load().mmrca_nonorm_fwd(ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), rows, D, ld_x, ld_res, ld_sum, ld_y,
+                                   dtype, stream_ptr()), "mmrca_nonorm_fwd")
+
+
+def nonorm_bwd_workspace_bytes(rows, D) -> int:
+    return int(load().mmrca_nonorm_bwd_workspace_bytes(rows, D))
+
+
+def nonorm_bwd(dy, s, gamma, dres, ds_out, dgamma, dbeta, dbias, ws, rows, D, ld_dy, ld_s, ld_dres, ld_ds, dtype):
+    """ds_out = dy * gamma (+ dres); dgamma += sum dy * s, dbeta += sum dy, dbias (optional) += gamma * sum dy; ws: workspace tensor"""
+    _dev(dy, "nonorm_bwd dy")
+    _check(load().mmrca_nonorm_bwd(ptr(dy), ptr(s), ptr(gamma), ptr(dres), ptr(ds_out), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(ws),
+                                   ws.numel() * ws.element_size(), rows, D, ld_dy, ld_s, ld_dres, ld_ds, dtype, stream_ptr()),
+           "mmrca_nonorm_bwd")
+
+
+def trigram_embed_fwd(ids, perm, word, out, M, B, T, E, vocab, dtype):
+    """ids int32 [B, T] (padded), perm int32 [M] or None, word [vocab, E] -> out [M, 3E] = word[next] | word[id] | word[prev]"""
+    _dev(ids, "trigram_embed_fwd ids")
+    _check(load().mmrca_trigram_embed_fwd(ptr(ids), ptr(perm), ptr(word), ptr(out), M, B, T, E, vocab, dtype, stream_ptr()),
+           "mmrca_trigram_embed_fwd")
+
+
+def trigram_embed_bwd(dout, ids, perm, dword, M, B, T, E, vocab, pad_id, dtype):
+    _dev(dout, "trigram_embed_bwd dout")
+    _check(load().mmrca_trigram_embed_bwd(ptr(dout), ptr(ids), ptr(perm), ptr(dword), M, B, T, E, vocab, pad_id, dtype, stream_ptr()),
+           "mmrca_trigram_embed_bwd")

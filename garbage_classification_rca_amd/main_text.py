@@ -8,7 +8,7 @@ only ``--tl`` unfreezes it, for the fine-tuning phase.  Backbones not built here
 """
 from __future__ import annotations
 
-from .classifiers import TEXT_FACTORIES
+from .classifiers import TEXT_FACTORIES, build_text_classifier
 from .single_modality import train
 
 # main_text.py:270-306: model -> (batch size, fine-tuning batch size, forced --acc_steps or None)
@@ -20,7 +20,7 @@ BATCHES = {k: v for k, v in REFERENCE_BATCHES.items() if k in TEXT_FACTORIES}
 
 
 def build_model(name, args, dtype, device):
-    return TEXT_FACTORIES[name](4, args.model_dropout, dtype=dtype, device=device)
+    return build_text_classifier(name, 4, args.model_dropout, dtype, device)
 
 
 def main(argv=None):

@@ -631,6 +631,37 @@ typedef struct {
 int mmrca_image_augment(void* in_u8, void* tmp_u8, const void* desc /* MmrcaAugDesc[B], device */, float* out, int B, int H, int W,
                         const float* mean3 /* host */, const float* std3 /* host */, void* stream);
 
+/* K8. MobileBERT's row operators (csrc/mobilebert.hip; transformers modeling_mobilebert.py).  bf16 | fp32 operands, fp32 arithmetic,
+ * 16-byte accesses when D / E, the row pitches (elements) and the pointers allow and an element-wise path otherwise; no host
+ * synchronisation and no allocation (capturable in a HIP graph).
+ *
+ * NoNorm (:55-62, the element-wise affine in place of every LayerNorm) behind the residual add:
+ *   s = x (+ res),  y = s * gamma + beta     on [rows, D] with row pitches ld_*.
+ * res may be NULL; sum_out (optional) receives s and may be the buffer of x; gamma / beta [D] in `dtype`. */
+int mmrca_nonorm_fwd(const void* x, const void* res, const void* gamma, const void* beta, void* sum_out, void* y, int64_t rows, int D,
+                     int64_t ld_x, int64_t ld_res, int64_t ld_sum, int64_t ld_y, int dtype, void* stream);
+/* backward: ds_out = dy * gamma (+ dres: an incoming residual-stream gradient, so that needs no separate add) -- the gradient of
+ * both x and res --, dgamma += sum_rows dy * s, dbeta += sum_rows dy, and (dbias optional) dbias += gamma * sum_rows dy = the
+ * column sums of dy * gamma, i.e. the bias gradient of the Linear that produced x, without a second pass.  dgamma / dbeta / dbias
+ * fp32 [D].  The column sums go through `workspace` (>= mmrca_nonorm_bwd_workspace_bytes(rows, D), fp32-aligned) in a fixed
+ * order, without atomics: bitwise reproducible.  Two launches. */
+int64_t mmrca_nonorm_bwd_workspace_bytes(int64_t rows, int D);
+int mmrca_nonorm_bwd(const void* dy, const void* s, const void* gamma, const void* dres, void* ds_out, float* dgamma, float* dbeta,
+                     float* dbias, void* workspace, int64_t workspace_bytes, int64_t rows, int D, int64_t ld_dy, int64_t ld_s,
+                     int64_t ld_dres, int64_t ld_ds, int dtype, void* stream);
+/* Trigram input embedding (:113-128).  ids: int32 [B, T], the PADDED id matrix; perm (optional): int32 [M], the index in B*T of
+ * each output row (TextPack.perm; NULL = padded layout, M = B*T); word [vocab, E] in `dtype`.
+ *   out[r] [3E] = word[ids[p + 1]] | word[ids[p]] | word[ids[p - 1]],  p = perm[r], zeros beyond the ends of the padded sequence
+ * (t = T - 1 / t = 0).  Neighbours always come from the padded matrix: a caption's last packed row reads its own padding id, never
+ * the next caption.  Ids or perm entries outside their range yield zeros.
+ * backward: the three column blocks of dout are added into dword (fp32 [vocab, E], +=) with fp32 atomicAdd -- ids repeat; the
+ * accumulation method of mmrca_embed_bwd, so the sum order (not the sum) may differ between runs.  Slots whose id == pad_id add
+ * nothing (nn.Embedding(padding_idx)); pad_id = -1: none. */
+int mmrca_trigram_embed_fwd(const int32_t* ids, const int32_t* perm, const void* word, void* out, int64_t M, int B, int T, int E,
+                            int vocab, int dtype, void* stream);
+int mmrca_trigram_embed_bwd(const void* dout, const int32_t* ids, const int32_t* perm, float* dword, int64_t M, int B, int T, int E,
+                            int vocab, int pad_id, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
