@@ -20,7 +20,6 @@
 // (16 lanes = 16 rows, same slot) are conflict-free, transposed-pattern reads (16 lanes = 16 slots of one row) at most 2-way;
 // the LDS array is idle most of the time next to the fp32 matrix pipe (one 16-byte read per four 32-cycle MFMAs).
 #include "common.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(4))) float f4;
 
@@ -341,10 +340,8 @@ mha_bwd_dkv_f32m_k(const float* __restrict__ qkv, const int32_t* __restrict__ ke
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-static const bool g_f32m_on = !(getenv("MMRCA_ATTN_F32_MFMA") && atoi(getenv("MMRCA_ATTN_F32_MFMA")) == 0);
-
 bool mmrca_mha_f32m_ok(int S, int dh, int dtype) {
-  return g_f32m_on && dtype == MMRCA_F32 && dh == F32A_DH && S >= 1 && S <= 208;
+  return dtype == MMRCA_F32 && dh == F32A_DH && S >= 1 && S <= 208;
 }
 
 static int nkt_for(int S) { return S <= 64 ? 4 : (S <= 128 ? 8 : 13); }

@@ -14,7 +14,6 @@
 //     dK/dV (a wave owns 16 keys, sweeps queries); no atomics, no fp32 scratch in HBM.
 // Masked keys get -inf; a query whose keys are all masked outputs zeros and lse=+inf (torch SDPA semantics).
 #include "common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -117,11 +116,8 @@ __device__ __forceinline__ void stage_key_bias(float* kb, const int32_t* __restr
 // NW waves per block share the two LDS images: LDS (2 x 28 KiB at S=197) allows two blocks per CU, so NW = 8 is what puts
 // four waves on every SIMD (the kernels are latency-bound on LDS reads between dependent MFMAs) and halves the number of
 // tiles a wave walks.
-// QT = query tiles (of 16) a wave processes together: with QT = 2 every K / V fragment read from LDS feeds two MFMAs (the
-// kernel is bound by LDS fragment traffic and VALU latency, not by MFMA issue), at the price of ~190 VGPRs = two waves per
-// SIMD instead of four.
-template <int NKT, bool DROP, int NW, int QT>     // key tiles of 16 (Spad = 16*NKT, NKT even); DROP: attention-probability dropout compiled in
-__global__ void __launch_bounds__(64 * NW, QT == 1 ? NW / 2 : NW / 4)
+template <int NKT, bool DROP, int NW>     // key tiles of 16 (Spad = 16*NKT, NKT even); DROP: attention-probability dropout compiled in
+__global__ void __launch_bounds__(64 * NW, NW / 2)
 mha_fwd_mfma_k(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ key_mask, bf16_t* __restrict__ out,
                float* __restrict__ lse, int H, int Smax, float scale, float drop_p, uint64_t drop_seed,
                const int32_t* __restrict__ cu) {
@@ -144,90 +140,72 @@ mha_fwd_mfma_k(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ key_m
   __syncthreads();
   const float c1 = scale * LOG2E;                    // scores live in the exp2 domain
   const int nqt = (S + 15) / 16;
-  for (int qg = wave; qg * QT < nqt; qg += NW) {
-    const int q0 = qg * QT * 16;
-    bf16x8 qf0[QT], qf1[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) { qf0[t] = frag_global(Q, ld, q0 + 16 * t, S, 0, lane); qf1[t] = frag_global(Q, ld, q0 + 16 * t, S, 1, lane); }
-    f32x4 s[QT][NKT];
+  for (int qt = wave; qt < nqt; qt += NW) {
+    const int q0 = qt * 16;
+    const bf16x8 qf0 = frag_global(Q, ld, q0, S, 0, lane), qf1 = frag_global(Q, ld, q0, S, 1, lane);
+    f32x4 s[NKT];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       const bf16x8 kf0 = frag_rows(Kimg, IMG_ROW, kt * 16, 0, lane), kf1 = frag_rows(Kimg, IMG_ROW, kt * 16, 1, lane);
-#pragma unroll
-      for (int t = 0; t < QT; ++t) {
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, qf0[t], a, 0, 0, 0);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, qf1[t], a, 0, 0, 0);
-        s[t][kt] = a;
-      }
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf0, qf0, a, 0, 0, 0);
+      a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf1, qf1, a, 0, 0, 0);
+      s[kt] = a;
       // keep the scheduler from hoisting every K fragment of the row up front (it then needs > 128 VGPRs and spills);
       // with four waves per SIMD the other waves cover this tile's LDS latency
       if (NW > 4 && (kt & 1)) __builtin_amdgcn_sched_barrier(0);
     }
-    float m[QT], l[QT];
+    float m = -INFINITY;
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      float mm = -INFINITY;
+    for (int kt = 0; kt < NKT; ++kt) {
+      const f32x4 bias = *reinterpret_cast<const f32x4*>(kb + kt * 16 + 4 * g);     // keys 16kt + 4g + r
 #pragma unroll
-      for (int kt = 0; kt < NKT; ++kt) {
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(kb + kt * 16 + 4 * g);     // keys 16kt + 4g + r
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = fmaf(s[t][kt][r], c1, bias[r]);
-          s[t][kt][r] = v;
-          mm = fmaxf(mm, v);
-        }
+      for (int r = 0; r < 4; ++r) {
+        const float v = fmaf(s[kt][r], c1, bias[r]);
+        s[kt][r] = v;
+        m = fmaxf(m, v);
       }
-      mm = colgroup_max(mm);
-      float ll = 0.f;
-      const float msafe = mm > -INFINITY ? mm : 0.f;
+    }
+    m = colgroup_max(m);
+    float l = 0.f;
+    const float msafe = m > -INFINITY ? m : 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float e = __builtin_amdgcn_exp2f(s[kt][r] - msafe); s[kt][r] = e; l += e; }
+    l = colgroup_sum(l);
+    if (DROP) {      // dropout acts on the normalised probabilities: mask the numerators, keep the denominator
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const float e = __builtin_amdgcn_exp2f(s[t][kt][r] - msafe); s[t][kt][r] = e; ll += e; }
-      ll = colgroup_sum(ll);
-      if (DROP) {      // dropout acts on the normalised probabilities: mask the numerators, keep the denominator
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            s[t][kt][r] *= attn_keep(drop_p, drop_sc, drop_seed, blockIdx.x, Smax, q0 + 16 * t + l16, kt * 16 + 4 * g + r);
-      }
-      m[t] = mm; l[t] = ll;
+        for (int r = 0; r < 4; ++r)
+          s[kt][r] *= attn_keep(drop_p, drop_sc, drop_seed, blockIdx.x, Smax, q0 + l16, kt * 16 + 4 * g + r);
     }
-    f32x4 o[QT][4];
+    f32x4 o[4];
 #pragma unroll
-    for (int t = 0; t < QT; ++t)
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) o[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < NKT / 2; ++u) {
-      bf16x8 pf[QT];
-#pragma unroll
-      for (int t = 0; t < QT; ++t) pf[t] = pack_pair(s[t][2 * u], s[t][2 * u + 1]);
+      const bf16x8 pf = pack_pair(s[2 * u], s[2 * u + 1]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         const bf16x8 vf = frag_cols_tr(Vimg, u, dt, lane);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[t], o[t][dt], 0, 0, 0);   // O^T[d][q]
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);   // O^T[d][q]
       }
       if (NW > 4) __builtin_amdgcn_sched_barrier(0);
     }
+    const int q = q0 + l16;
+    if (q < S) {
+      const float inv = l > 0.f ? 1.f / l : 0.f;
+      bf16_t* orow = out + ((int64_t)row0 + q) * (H * AT_DH) + h * AT_DH;
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const int q = q0 + 16 * t + l16;
-      if (q < S) {
-        const float inv = l[t] > 0.f ? 1.f / l[t] : 0.f;
-        bf16_t* orow = out + ((int64_t)row0 + q) * (H * AT_DH) + h * AT_DH;
+      for (int dt = 0; dt < 4; ++dt) {
+        bf16x4 v;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          bf16x4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = (bf16_t)(o[t][dt][r] * inv);
-          *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * g) = v;
-        }
-        if (g == 0) lse[((int64_t)b * H + h) * Smax + q] = l[t] > 0.f ? m[t] * LN2 + __logf(l[t]) : INFINITY;
+        for (int r = 0; r < 4; ++r) v[r] = (bf16_t)(o[dt][r] * inv);
+        *reinterpret_cast<bf16x4*>(orow + dt * 16 + 4 * g) = v;
       }
+      if (g == 0) lse[((int64_t)b * H + h) * Smax + q] = l > 0.f ? m * LN2 + __logf(l) : INFINITY;
     }
   }
 }
@@ -858,262 +836,39 @@ mha_bwd_dkv_mfma_k(const bf16_t* __restrict__ qkv, const int32_t* __restrict__ k
 }
 
 // ------------------------------------------------------------------------------------------------------
-// backward, dK/dV for the ViT (unmasked, no dropout, padded layout): hand-scheduled inner loop
+// backward for the ViT as ONE launch (unmasked, no dropout, padded layout)
 // ------------------------------------------------------------------------------------------------------
-// Same work split as mha_bwd_dkv_mfma_k (a wave owns 16 keys, sweeps the query tiles in pairs), but the inner loop is laid
-// out by hand: hipcc's schedule of the C++ version waits on every LDS read right in front of the MFMA that consumes it (19
-// s_waitcnt per query pair at 108 VGPRs).  Here a query pair issues its 8 row fragments and its row constants in one batch,
-// and the 16 transposed fragments of the dV / dK products right after the S / dP MFMAs, so that they land under the
+// A two-kernel form (a dQ and a dK/dV launch) reads q|k|v, O and dO twice (~1.0 GB per ViT-B layer at B = 256) where the algorithm
+// needs them once (0.62 GB incl. the dqkv store), and in-kernel stamps (tools/attn_stamps.py) show where a workgroup's time goes:
+// not in the MFMA loops (6-8 k cycles per part with every operand in LDS) but in waiting -- for the staging DMA and for the per-tile
+// operand fragments that come straight from HBM.  One workgroup per (b, h) runs BOTH parts, so every operand crosses HBM once.  S
+// and dP are still formed in both orientations (28 MFMA passes instead of the 20 of a single-orientation kernel): the matrix pipe
+// idles ~75 % of these kernels' time, the bytes and the exposed latencies are what count.  No atomics, no cross-wave reduction,
+// same summation order per output element.
+// Same work split as mha_bwd_dq_mfma_k / mha_bwd_dkv_mfma_k (a wave owns 16 queries / keys and sweeps the opposite tiles in pairs),
+// but the inner loops are laid out by hand: hipcc's schedule of the C++ version waits on every LDS read right in front of the MFMA
+// that consumes it (19 s_waitcnt per query pair at 108 VGPRs).  Here a pair issues its 8 row fragments and its row constants in one
+// batch, and the transposed fragments of the second products right after the S / dP MFMAs, so that they land under the
 // exponentials; the tile / pair index is an immediate offset of the asm ds_read (no address arithmetic in the loop).
 // Row constants as the initial accumulator (the guide's attention-backward recipe): the prologue stores -lse/c1 and
 // -rowsum(dO*O) per query, the S and dP MFMA chains start from them, and p = exp2(c1 * S'), dS = p * dP' need no subtraction.
+// Two 8-wave workgroups per CU, so one's staging runs under the other's MFMAs.  The image pairs TIME-SHARE one 56-KiB region:
+// K | V are staged first, together with the per-query constants (from whole dO / O rows), for the dQ part, whose Q / dO fragments
+// come from global memory; after a barrier Q | dO are staged over them for the dK / dV part, whose key / value fragments hit this
+// XCD's L2 (staged moments ago).  (A 16-wave form with all four images resident and no global fragment loads was measured slower
+// in round 3: nothing overlapped its staging.)
 template <int NKT, int NW>
 __global__ void __launch_bounds__(64 * NW, NW / 2)
-mha_bwd_dkv_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
-                     const float* __restrict__ lse, bf16_t* __restrict__ dqkv, int H, int S, float scale) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];
-  constexpr int Spad = NKT * 16, IMG = Spad * 128;
-  char* Qimg = sm; char* Dimg = sm + IMG;
-  float* lse_s = reinterpret_cast<float*>(sm + 2 * IMG);     // -lse / c1 in the exp2 domain (c1 * (S + this) = c1 S - L)
-  float* dsum_s = lse_s + Spad;                              // -rowsum(dO * O)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int row0 = b * S;
-  const int64_t ld = 3LL * H * AT_DH, ldo = (int64_t)H * AT_DH;
-  const bf16_t* Q = qkv + (int64_t)row0 * ld + h * AT_DH;
-  const bf16_t* Kp = Q + H * AT_DH;
-  const bf16_t* Vp = Kp + H * AT_DH;
-  const bf16_t* O = out + (int64_t)row0 * ldo + h * AT_DH;
-  const bf16_t* dO = dout + (int64_t)row0 * ldo + h * AT_DH;
-  const float c1 = scale * LOG2E, inv_c1 = 1.f / c1;
-  stage_rows(Qimg, IMG_TR, Q, ld, S, Spad);
-  stage_rows(Dimg, IMG_TR, dO, ldo, S, Spad);
-  for (int q = threadIdx.x; q < Spad; q += blockDim.x) {
-    float a = 0.f, L = INFINITY;                 // padded query rows: lse=+inf -> P = 0
-    if (q < S) {
-      L = lse[((int64_t)b * H + h) * S + q] * LOG2E;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const bf16x8 x = *reinterpret_cast<const bf16x8*>(dO + (int64_t)q * ldo + c * 8);
-        const bf16x8 y = *reinterpret_cast<const bf16x8*>(O + (int64_t)q * ldo + c * 8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a += (float)x[j] * (float)y[j];
-      }
-    }
-    lse_s[q] = -L * inv_c1; dsum_s[q] = -a;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const unsigned lds0 = (unsigned)(uintptr_t)(at_lds_void*)sm;
-  // per-lane byte offsets inside an image (see mha_fwd_mfma_p_k: the XOR swizzles do not depend on the tile / pair index)
-  const unsigned rsw = (l16 >> 1) & 3;
-  const unsigned roff0 = l16 * 128 + ((((unsigned)(g >> 1)) ^ rsw) << 5) + ((g & 1) << 4);           // k-step 0: chunk c = g
-  const unsigned roff1 = l16 * 128 + ((((unsigned)(2 + (g >> 1))) ^ rsw) << 5) + ((g & 1) << 4);     // k-step 1: chunk c = 4 + g
-  const int qq = l16 >> 2, pp = l16 & 3, vsw = (2 * g + (qq >> 1)) & 3;
-  unsigned tq[4], td[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) {
-    const unsigned o = (4 * g + qq) * 128 + ((dt ^ vsw) << 5) + 8 * pp;
-    tq[dt] = lds0 + o; td[dt] = lds0 + IMG + o;
-  }
-  const unsigned qb0 = lds0 + roff0, qb1 = lds0 + roff1, db0 = lds0 + IMG + roff0, db1 = lds0 + IMG + roff1;
-  const unsigned lb = lds0 + 2 * IMG + 16 * g, sb = lb + Spad * 4;      // row constants of queries 16 qt + 4 g + r
-  const int nkt = (S + 15) / 16;
-  for (int kt = wave; kt < nkt; kt += NW) {
-    const int k0 = kt * 16;
-    const int key = k0 + l16;
-    const float kbias = key < S ? 0.f : -INFINITY;                        // this lane's key
-    const bf16x8 kf0 = frag_global(Kp, ld, k0, S, 0, lane), kf1 = frag_global(Kp, ld, k0, S, 1, lane);
-    const bf16x8 vf0 = frag_global(Vp, ld, k0, S, 0, lane), vf1 = frag_global(Vp, ld, k0, S, 1, lane);
-    f32x4 dk[4], dv[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { dk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-    static_for<0, NKT / 2>([&](auto ic) {
-      constexpr int u = decltype(ic)::value;
-      bf16x8 qa0, qa1, qb0_, qb1_, da0, da1, db0_, db1_;      // row fragments of query tiles 2u (a) and 2u+1 (b), k-steps 0 / 1
-      f32x4 sa, sb_, pa, pb;                                  // S' and dP' accumulators, started from the row constants
-      AT_DS_B128_OFF(qa0, qb0, (2 * u) * 2048);     AT_DS_B128_OFF(da0, db0, (2 * u) * 2048);
-      AT_DS_B128_OFF(qb0_, qb0, (2 * u + 1) * 2048); AT_DS_B128_OFF(db0_, db0, (2 * u + 1) * 2048);
-      AT_DS_B128_OFF(sa, lb, (2 * u) * 64);          AT_DS_B128_OFF(pa, sb, (2 * u) * 64);
-      AT_DS_B128_OFF(sb_, lb, (2 * u + 1) * 64);     AT_DS_B128_OFF(pb, sb, (2 * u + 1) * 64);
-      AT_DS_B128_OFF(qa1, qb1, (2 * u) * 2048);     AT_DS_B128_OFF(da1, db1, (2 * u) * 2048);
-      AT_DS_B128_OFF(qb1_, qb1, (2 * u + 1) * 2048); AT_DS_B128_OFF(db1_, db1, (2 * u + 1) * 2048);
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(qa0), "+v"(da0), "+v"(qb0_), "+v"(db0_), "+v"(sa), "+v"(pa), "+v"(sb_), "+v"(pb));
-      sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa0, kf0, sa, 0, 0, 0);       // S'[q][key]
-      pa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da0, vf0, pa, 0, 0, 0);       // dP'[q][key]
-      sb_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qb0_, kf0, sb_, 0, 0, 0);
-      pb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(db0_, vf0, pb, 0, 0, 0);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qa1), "+v"(da1), "+v"(qb1_), "+v"(db1_));
-      sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa1, kf1, sa, 0, 0, 0);
-      pa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da1, vf1, pa, 0, 0, 0);
-      sb_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qb1_, kf1, sb_, 0, 0, 0);
-      pb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(db1_, vf1, pb, 0, 0, 0);
-      // the transposed fragments of the second products do not depend on P: in flight under the exponentials
-      bf16x4 dlo[4], dhi[4], qlo[4], qhi[4];
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        AT_DS_TR_OFF(dlo[dt], td[dt], u * 4096); AT_DS_TR_OFF(dhi[dt], td[dt], u * 4096 + 2048);
-        AT_DS_TR_OFF(qlo[dt], tq[dt], u * 4096); AT_DS_TR_OFF(qhi[dt], tq[dt], u * 4096 + 2048);
-      }
-      f32x4 p2a, p2b, dsa, dsb;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        p2a[r] = __builtin_amdgcn_exp2f(fmaf(sa[r], c1, kbias));            // 0 for dead keys and padded queries
-        p2b[r] = __builtin_amdgcn_exp2f(fmaf(sb_[r], c1, kbias));
-        dsa[r] = p2a[r] * pa[r];                                            // (the score scale is applied to dK below)
-        dsb[r] = p2b[r] * pb[r];
-      }
-      const bf16x8 pf = pack_pair(p2a, p2b), dsf = pack_pair(dsa, dsb);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dlo[0]), "+v"(dhi[0]), "+v"(dlo[1]), "+v"(dhi[1]), "+v"(dlo[2]), "+v"(dhi[2]), "+v"(dlo[3]), "+v"(dhi[3]),
-                   "+v"(qlo[0]), "+v"(qhi[0]), "+v"(qlo[1]), "+v"(qhi[1]), "+v"(qlo[2]), "+v"(qhi[2]), "+v"(qlo[3]), "+v"(qhi[3]));
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_shufflevector(dlo[dt], dhi[dt], 0, 1, 2, 3, 4, 5, 6, 7), pf, dv[dt], 0, 0, 0);    // dV^T[d][key]
-        dk[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_shufflevector(qlo[dt], qhi[dt], 0, 1, 2, 3, 4, 5, 6, 7), dsf, dk[dt], 0, 0, 0);   // dK^T[d][key]
-      }
-    });
-    bf16_t* krow = dqkv + ((int64_t)row0 + (key < S ? key : S - 1)) * ld + (int64_t)H * AT_DH + h * AT_DH;
-    bf16_t* vrow = krow + (int64_t)H * AT_DH;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      bf16x4 a, c;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { a[r] = (bf16_t)(dk[dt][r] * scale); c[r] = (bf16_t)dv[dt][r]; }
-      if (key < S) {
-        *reinterpret_cast<bf16x4*>(krow + dt * 16 + 4 * g) = a;
-        *reinterpret_cast<bf16x4*>(vrow + dt * 16 + 4 * g) = c;
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// backward, dQ for the ViT (unmasked, no dropout, padded layout): hand-scheduled inner loop (see mha_bwd_dkv_mfma_v_k)
-// ------------------------------------------------------------------------------------------------------
-template <int NKT, int NW>
-__global__ void __launch_bounds__(64 * NW, NW / 2)
-mha_bwd_dq_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
-                    const float* __restrict__ lse, bf16_t* __restrict__ dqkv, int H, int S, float scale) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];
-  constexpr int Spad = NKT * 16, IMG = Spad * 128;
-  char* Kimg = sm; char* Vimg = sm + IMG;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int row0 = b * S;
-  const int64_t ld = 3LL * H * AT_DH, ldo = (int64_t)H * AT_DH;
-  const bf16_t* Q = qkv + (int64_t)row0 * ld + h * AT_DH;
-  const bf16_t* Kp = Q + H * AT_DH;
-  const bf16_t* Vp = Kp + H * AT_DH;
-  const bf16_t* O = out + (int64_t)row0 * ldo + h * AT_DH;
-  const bf16_t* dO = dout + (int64_t)row0 * ldo + h * AT_DH;
-  stage_rows(Kimg, IMG_TR, Kp, ld, S, Spad);      // row reads for S^T (2-way), transposed reads for dQ^T
-  stage_rows(Vimg, IMG_ROW, Vp, ld, S, Spad);     // row reads for dP^T
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const float c1 = scale * LOG2E, inv_c1 = 1.f / c1;
-  const unsigned lds0 = (unsigned)(uintptr_t)(at_lds_void*)sm;
-  const unsigned rsw = (l16 >> 1) & 3, ksw = (l16 >> 1) & 7;
-  const unsigned kb0 = lds0 + l16 * 128 + ((((unsigned)(g >> 1)) ^ rsw) << 5) + ((g & 1) << 4);          // K (TR image) rows, k-step 0
-  const unsigned kb1 = lds0 + l16 * 128 + ((((unsigned)(2 + (g >> 1))) ^ rsw) << 5) + ((g & 1) << 4);    // k-step 1
-  const unsigned vb0 = lds0 + IMG + l16 * 128 + (((unsigned)g ^ ksw) << 4);                                // V (ROW image) rows
-  const unsigned vb1 = lds0 + IMG + l16 * 128 + (((unsigned)(4 + g) ^ ksw) << 4);
-  const int qq = l16 >> 2, pp = l16 & 3, vsw = (2 * g + (qq >> 1)) & 3;
-  unsigned tk[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) tk[dt] = lds0 + (4 * g + qq) * 128 + ((dt ^ vsw) << 5) + 8 * pp;
-  const int nqt = (S + 15) / 16;
-  for (int qt = wave; qt < nqt; qt += NW) {
-    const int q0 = qt * 16;
-    const int q = q0 + l16;
-    const bf16x8 qf0 = frag_global(Q, ld, q0, S, 0, lane), qf1 = frag_global(Q, ld, q0, S, 1, lane);
-    const bf16x8 df0 = frag_global(dO, ldo, q0, S, 0, lane), df1 = frag_global(dO, ldo, q0, S, 1, lane);
-    const bf16x8 of0 = frag_global(O, ldo, q0, S, 0, lane), of1 = frag_global(O, ldo, q0, S, 1, lane);
-    float dsum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) dsum += (float)df0[j] * (float)of0[j] + (float)df1[j] * (float)of1[j];
-    dsum = colgroup_sum(dsum);                       // D_q = rowsum(dO * O)
-    // row constants as the initial accumulators: S' = S - L/c1 (so p = exp2(c1 S')), dP' = dP - D
-    const float nl = -(lse[((int64_t)b * H + h) * S + (q < S ? q : S - 1)] * LOG2E) * inv_c1, nd = -dsum;
-    f32x4 dq[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    static_for<0, NKT / 2>([&](auto ic) {
-      constexpr int u = decltype(ic)::value;
-      bf16x8 ka0, ka1, kc0, kc1, va0, va1, vc0, vc1;         // key tiles 2u (a) and 2u+1 (c), k-steps 0 / 1
-      AT_DS_B128_OFF(ka0, kb0, (2 * u) * 2048);     AT_DS_B128_OFF(va0, vb0, (2 * u) * 2048);
-      AT_DS_B128_OFF(kc0, kb0, (2 * u + 1) * 2048); AT_DS_B128_OFF(vc0, vb0, (2 * u + 1) * 2048);
-      AT_DS_B128_OFF(ka1, kb1, (2 * u) * 2048);     AT_DS_B128_OFF(va1, vb1, (2 * u) * 2048);
-      AT_DS_B128_OFF(kc1, kb1, (2 * u + 1) * 2048); AT_DS_B128_OFF(vc1, vb1, (2 * u + 1) * 2048);
-      f32x4 sa = {nl, nl, nl, nl}, sc_ = {nl, nl, nl, nl}, pa = {nd, nd, nd, nd}, pc = {nd, nd, nd, nd};
-      asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(ka0), "+v"(va0), "+v"(kc0), "+v"(vc0));
-      sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka0, qf0, sa, 0, 0, 0);       // S'^T[key][q]
-      pa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va0, df0, pa, 0, 0, 0);       // dP'^T[key][q]
-      sc_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kc0, qf0, sc_, 0, 0, 0);
-      pc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vc0, df0, pc, 0, 0, 0);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ka1), "+v"(va1), "+v"(kc1), "+v"(vc1));
-      sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka1, qf1, sa, 0, 0, 0);
-      pa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va1, df1, pa, 0, 0, 0);
-      sc_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kc1, qf1, sc_, 0, 0, 0);
-      pc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vc1, df1, pc, 0, 0, 0);
-      bf16x4 klo[4], khi[4];                       // K^T fragments of the dQ product: in flight under the exponentials
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) { AT_DS_TR_OFF(klo[dt], tk[dt], u * 4096); AT_DS_TR_OFF(khi[dt], tk[dt], u * 4096 + 2048); }
-      f32x4 dsa, dsc;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float xa = sa[r] * c1, xc = sc_[r] * c1;
-        if (u == NKT / 2 - 1) {                    // only the last key pair holds keys beyond S (S > 16 (NKT - 2))
-          xa = (2 * u) * 16 + 4 * g + r < S ? xa : -INFINITY;
-          xc = (2 * u + 1) * 16 + 4 * g + r < S ? xc : -INFINITY;
-        }
-        dsa[r] = __builtin_amdgcn_exp2f(xa) * pa[r];        // p (dP - D); a padded query has lse = +inf -> p = 0
-        dsc[r] = __builtin_amdgcn_exp2f(xc) * pc[r];        // (the score scale is applied to dQ below)
-      }
-      const bf16x8 dsf = pack_pair(dsa, dsc);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(klo[0]), "+v"(khi[0]), "+v"(klo[1]), "+v"(khi[1]), "+v"(klo[2]), "+v"(khi[2]), "+v"(klo[3]), "+v"(khi[3]));
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-        dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_shufflevector(klo[dt], khi[dt], 0, 1, 2, 3, 4, 5, 6, 7), dsf, dq[dt], 0, 0, 0);   // dQ^T[d][q]
-    });
-    bf16_t* drow = dqkv + ((int64_t)row0 + (q < S ? q : S - 1)) * ld + h * AT_DH;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      bf16x4 v;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = (bf16_t)(dq[dt][r] * scale);
-      if (q < S) *reinterpret_cast<bf16x4*>(drow + dt * 16 + 4 * g) = v;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// backward for the ViT as ONE launch (unmasked, no dropout, padded layout)
-// ------------------------------------------------------------------------------------------------------
-// The two-kernel form reads q|k|v, O and dO twice (~1.0 GB per ViT-B layer at B = 256) where the algorithm needs them once
-// (0.62 GB incl. the dqkv store), and in-kernel stamps (tools/attn_stamps.py) show where a workgroup's time goes: not in the
-// MFMA loops (6-8 k cycles per part with every operand in LDS) but in waiting -- for the staging DMA and for the per-tile
-// operand fragments that come straight from HBM.  One workgroup per (b, h) runs BOTH parts -- the hand-scheduled loops of the two
-// kernels above -- so every operand crosses HBM once.  S and dP are still formed in both orientations (28 MFMA passes
-// instead of the 20 of a single-orientation kernel): the matrix pipe idles ~75 % of these kernels' time, the bytes and the
-// exposed latencies are what count.  No atomics, no cross-wave reduction, same summation order per output element.
-//   SHARE = true (default): two 8-wave workgroups per CU, so one's staging runs under the other's MFMAs.  The image pairs
-//     TIME-SHARE one 56-KiB region: K | V are staged first, together with the per-query constants (from whole dO / O rows), for
-//     the dQ part, whose Q / dO fragments come from global memory; after a barrier Q | dO are staged over them for the dK / dV
-//     part, whose key / value fragments hit this XCD's L2 (staged moments ago).
-//   SHARE = false: one 16-wave workgroup per CU with all four images resident (4 x 28 KiB), no global fragment loads at all;
-//     nothing overlaps its staging, so it is the slower of the two (MMRCA_ATTN_BWD_FUSED=2 selects it).
-template <int NKT, int NW, bool SHARE>
-__global__ void __launch_bounds__(64 * NW, SHARE ? NW / 2 : NW / 4)
 mha_bwd_fused_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
                        const float* __restrict__ lse, bf16_t* __restrict__ dqkv, int H, int S, float scale,
-                       unsigned long long* __restrict__ stamps, int prefetch) {
+                       unsigned long long* __restrict__ stamps) {
   // stamps (tools/attn_stamps.py only, nullptr otherwise): s_memtime of wave 0 at kernel entry, after the first staging barrier,
   // between the two parts and at exit, [block][4]; written to a buffer nothing else reads
   unsigned long long t_in = 0, t_staged = 0, t_mid = 0;
   if (stamps) t_in = __builtin_amdgcn_s_memtime();
   extern __shared__ __attribute__((aligned(16))) char sm[];
   constexpr int Spad = NKT * 16, IMG = Spad * 128;
-  constexpr int KB = 0, VB = IMG, QB = SHARE ? 0 : 2 * IMG, DB = SHARE ? IMG : 3 * IMG, ST = SHARE ? 2 * IMG : 4 * IMG;
+  constexpr int KB = 0, VB = IMG, QB = 0, DB = IMG, ST = 2 * IMG;      // Q | dO over K | V
   float* lse_s = reinterpret_cast<float*>(sm + ST);          // -lse / c1 in the exp2 domain (c1 * (S + this) = c1 S - L)
   float* dsum_s = lse_s + Spad;                              // -rowsum(dO * O)
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
@@ -1161,7 +916,7 @@ mha_bwd_fused_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict_
     }
   };
 
-  // SHARE: the per-tile operand fragments that come straight from global memory are PREFETCHED -- a wave's first query tile
+  // The per-tile operand fragments that come straight from global memory are PREFETCHED -- a wave's first query tile
   // (Q | dO rows) at kernel entry, under the staging DMA; its first key tile (K | V rows) before the second staging -- so that their latency (in-kernel stamps: ~25 k of a workgroup's ~57 k
   // cycles were spent waiting for exactly these loads) is not exposed for the first tiles (8 of the 13 per part).
   bf16x8 pq0, pq1, pd0, pd1, pk0, pk1, pv0, pv1;
@@ -1235,18 +990,12 @@ mha_bwd_fused_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict_
         if (q < S) *reinterpret_cast<bf16x4*>(drow + dt * 16 + 4 * g) = v;
       }
     };
-    if constexpr (SHARE) {
-      // the Q | dO images are gone: fragments from global memory -- the first tile's were prefetched at kernel entry; a second
-      // tile's are loaded here (prefetching them too costs 16 live registers inside the loop: spills)
-      if (wave < nt) { if (!prefetch) fetch_q(wave); dq_tile(wave, pq0, pq1, pd0, pd1); }
-      for (int qt = wave + NW; qt < nt; qt += NW)
-        dq_tile(qt, frag_global(Q, ld, qt * 16, S, 0, lane), frag_global(Q, ld, qt * 16, S, 1, lane), frag_global(dO, ldo, qt * 16, S, 0, lane),
-                frag_global(dO, ldo, qt * 16, S, 1, lane));
-    } else {
-      for (int qt = wave; qt < nt; qt += NW)
-        dq_tile(qt, frag_rows(sm + QB, IMG_TR, qt * 16, 0, lane), frag_rows(sm + QB, IMG_TR, qt * 16, 1, lane), frag_rows(sm + DB, IMG_TR, qt * 16, 0, lane),
-                frag_rows(sm + DB, IMG_TR, qt * 16, 1, lane));
-    }
+    // the Q | dO images are not staged yet: fragments from global memory -- the first tile's were prefetched at kernel entry; a
+    // second tile's are loaded here (prefetching them too costs 16 live registers inside the loop: spills)
+    if (wave < nt) dq_tile(wave, pq0, pq1, pd0, pd1);
+    for (int qt = wave + NW; qt < nt; qt += NW)
+      dq_tile(qt, frag_global(Q, ld, qt * 16, S, 0, lane), frag_global(Q, ld, qt * 16, S, 1, lane), frag_global(dO, ldo, qt * 16, S, 0, lane),
+              frag_global(dO, ldo, qt * 16, S, 1, lane));
   };
 
   // ---- dK / dV: a wave's key tile(s) against every query pair (Q | dO images, row constants in LDS)
@@ -1322,44 +1071,26 @@ mha_bwd_fused_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict_
         }
       }
     };
-    if constexpr (SHARE) {
-      if (wave < nt) { if (!prefetch) fetch_k(wave); dkv_tile(wave, pk0, pk1, pv0, pv1); }
-      for (int kt = wave + NW; kt < nt; kt += NW)
-        dkv_tile(kt, frag_global(Kp, ld, kt * 16, S, 0, lane), frag_global(Kp, ld, kt * 16, S, 1, lane), frag_global(Vp, ld, kt * 16, S, 0, lane),
-                 frag_global(Vp, ld, kt * 16, S, 1, lane));
-    } else {
-      for (int kt = wave; kt < nt; kt += NW)
-        dkv_tile(kt, frag_rows(sm + KB, IMG_TR, kt * 16, 0, lane), frag_rows(sm + KB, IMG_TR, kt * 16, 1, lane), frag_rows(sm + VB, IMG_ROW, kt * 16, 0, lane),
-                 frag_rows(sm + VB, IMG_ROW, kt * 16, 1, lane));
-    }
+    if (wave < nt) dkv_tile(wave, pk0, pk1, pv0, pv1);
+    for (int kt = wave + NW; kt < nt; kt += NW)
+      dkv_tile(kt, frag_global(Kp, ld, kt * 16, S, 0, lane), frag_global(Kp, ld, kt * 16, S, 1, lane), frag_global(Vp, ld, kt * 16, S, 0, lane),
+               frag_global(Vp, ld, kt * 16, S, 1, lane));
   };
 
-  if constexpr (SHARE) {
-    if (prefetch && wave < nt) fetch_q(wave);       // lands under the staging below
-    stage_key_side();
-    stage_row_constants();              // reads whole dO / O rows: the dO fragments of the dQ part then hit L2
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (stamps) t_staged = __builtin_amdgcn_s_memtime();
-    dq_part();
-    if (prefetch && wave < nt) fetch_k(wave);       // lands under the second staging
-    __syncthreads();                    // every wave is done with the K | V images (the row constants stay)
-    stage_query_images();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (stamps) t_mid = __builtin_amdgcn_s_memtime();
-    dkv_part();
-  } else {
-    stage_key_side();
-    stage_query_images();
-    stage_row_constants();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (stamps) t_staged = __builtin_amdgcn_s_memtime();
-    dq_part();
-    if (stamps) t_mid = __builtin_amdgcn_s_memtime();
-    dkv_part();
-  }
+  if (wave < nt) fetch_q(wave);         // lands under the staging below
+  stage_key_side();
+  stage_row_constants();                // reads whole dO / O rows: the dO fragments of the dQ part then hit L2
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (stamps) t_staged = __builtin_amdgcn_s_memtime();
+  dq_part();
+  if (wave < nt) fetch_k(wave);         // lands under the second staging
+  __syncthreads();                      // every wave is done with the K | V images (the row constants stay)
+  stage_query_images();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (stamps) t_mid = __builtin_amdgcn_s_memtime();
+  dkv_part();
   if (stamps && threadIdx.x == 0) {
     const unsigned long long t_out = __builtin_amdgcn_s_memtime();
     stamps[4 * blockIdx.x + 0] = t_in; stamps[4 * blockIdx.x + 1] = t_staged; stamps[4 * blockIdx.x + 2] = t_mid; stamps[4 * blockIdx.x + 3] = t_out;
@@ -1371,6 +1102,16 @@ mha_bwd_fused_mfma_v_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict_
 // ------------------------------------------------------------------------------------------------------
 bool mmrca_mha_mfma_ok(int S, int dh, int dtype) { return dtype == MMRCA_BF16 && dh == AT_DH && S >= 1 && S <= AT_MAX_S; }
 
+// CU count of the current device at the first call (the persistent kernels' grid bound), 256 if the query fails
+static int attn_cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    (void)hipGetDevice(&dev);
+    return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 1 ? n : 256;
+  }();
+  return ncu;
+}
+
 static int pick_nkt(int S) {
   const int need = (S + 31) / 32 * 2;            // key tiles, even
   const int opts[] = {2, 4, 8, 14, 16, 32};
@@ -1378,7 +1119,7 @@ static int pick_nkt(int S) {
   return 32;
 }
 
-#define K_FWD(N_, D_, W_) mha_fwd_mfma_k<N_, D_, W_, 1>
+#define K_FWD(N_, D_, W_) mha_fwd_mfma_k<N_, D_, W_>
 #define K_DQ(N_, D_, W_) mha_bwd_dq_mfma_k<N_, D_, W_>
 #define K_DKV(N_, D_, W_) mha_bwd_dkv_mfma_k<N_, D_, W_>
 #define AT_LAUNCH1(KERNEL, NKT, DROP, NW, LDSBYTES, ...)                                                                        \
@@ -1826,24 +1567,12 @@ int mmrca_mha_fwd_mfma(const void* qkv, const int32_t* key_mask, void* out, floa
   (void)dh;
   MMRCA_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 7) == 0, "mha_fwd: qkv must be 16-byte aligned");
   const int nkt = pick_nkt(S);
-  static const int persist = getenv("MMRCA_ATTN_PERSIST") ? atoi(getenv("MMRCA_ATTN_PERSIST")) : 1;
-  if (persist && nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12) {     // the ViT's attention: 197 tokens, no mask
-    static int ncu = 0;
-    if (ncu == 0) { int d = 0; (void)hipGetDevice(&d); if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || ncu < 1) ncu = 256; }
+  if (nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12) {     // the ViT's attention: 197 tokens, no mask
     const int ldsb = 4 * 14 * 16 * 128;
-    const int nbh = B * H, grid = nbh < ncu ? nbh : ncu;
+    const int nbh = B * H, grid = nbh < attn_cu_count() ? nbh : attn_cu_count();
     MMRCA_MAX_LDS(ldsb, mha_fwd_mfma_p_k<14, 16>);
     hipLaunchKernelGGL((mha_fwd_mfma_p_k<14, 16>), dim3(grid), dim3(1024), ldsb, st, (const bf16_t*)qkv, (bf16_t*)out, lse, H, S, scale, nbh);
     MMRCA_CHECK_LAUNCH("mha_fwd(mfma,persistent)");
-    return 0;
-  }
-  static const int qt2 = getenv("MMRCA_ATTN_QT2") ? atoi(getenv("MMRCA_ATTN_QT2")) : 0;
-  if (qt2 && nkt == 14 && drop_p <= 0.f) {        // two query tiles per wave (S in 193..224: the ViT's 197 tokens)
-    const int ldsb = 2 * 14 * 16 * 128 + BIAS_EXTRA(14);
-    MMRCA_MAX_LDS(ldsb, mha_fwd_mfma_k<14, false, 8, 2>);
-    hipLaunchKernelGGL((mha_fwd_mfma_k<14, false, 8, 2>), dim3(B * H), dim3(512), ldsb, st, (const bf16_t*)qkv, key_mask, (bf16_t*)out, lse, H, S,
-                       scale, drop_p, drop_seed, cu);
-    MMRCA_CHECK_LAUNCH("mha_fwd(mfma,qt2)");
     return 0;
   }
   AT_SWITCH(K_FWD, BIAS_EXTRA, true, false, false, (const bf16_t*)qkv, key_mask, (bf16_t*)out, lse, H, S, scale, drop_p, drop_seed, cu);
@@ -1858,12 +1587,9 @@ int mmrca_mha_fwd_x3_launch(const void* qkv_hi, const void* qkv_lo, const int32_
   MMRCA_REQUIRE(mmrca_mha_x3_ok(S, dh), "mha_fwd_x3: needs head dim 64 and 1 <= S <= 224 (got S=%d dh=%d)", S, dh);
   MMRCA_REQUIRE(((((uintptr_t)qkv_hi) | ((uintptr_t)qkv_lo)) & 15) == 0 && ((((uintptr_t)out_hi) | ((uintptr_t)out_lo)) & 7) == 0, "mha_fwd_x3: alignment");
   const int nkt = pick_nkt(S);
-  static const int x3_persist = getenv("MMRCA_ATTN_X3_PERSIST") ? atoi(getenv("MMRCA_ATTN_X3_PERSIST")) : 1;
-  if (x3_persist && nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12) {     // the ViT's attention: 197 tokens, no mask
-    static int ncu = 0;
-    if (ncu == 0) { int d = 0; (void)hipGetDevice(&d); if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || ncu < 1) ncu = 256; }
+  if (nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12) {     // the ViT's attention: 197 tokens, no mask
     const int ldsb = 4 * 14 * 16 * 128;
-    const int nbh = B * H, grid = nbh < ncu ? nbh : ncu;
+    const int nbh = B * H, grid = nbh < attn_cu_count() ? nbh : attn_cu_count();
     MMRCA_MAX_LDS(ldsb, mha_fwd_x3_p_k<14, 16>);
     hipLaunchKernelGGL((mha_fwd_x3_p_k<14, 16>), dim3(grid), dim3(1024), ldsb, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, (bf16_t*)out_hi,
                        (bf16_t*)out_lo, lse, H, S, scale, nbh);
@@ -1900,23 +1626,11 @@ int mmrca_mha_bwd_mfma(const void* qkv, const int32_t* key_mask, const void* out
   MMRCA_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)dout) & 15) == 0 && (((uintptr_t)dqkv) & 7) == 0,
                 "mha_bwd: buffers must be 16-byte aligned");
   const int nkt = pick_nkt(S);
-  static const int bwd_v = getenv("MMRCA_ATTN_BWD_V") ? atoi(getenv("MMRCA_ATTN_BWD_V")) : 1;
-  const bool use_v = bwd_v && nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12;      // the ViT's attention
-  // 3 (default): persistent workgroups, every operand read once (mha_bwd_p_mfma_v_k); 1: one launch, two time-sharing workgroups per
-  // CU (round 3's default; also what S in (208, 224] runs); 2: one 16-wave workgroup per CU; 0: the two-kernel form
-  static const int bwd_fused = getenv("MMRCA_ATTN_BWD_FUSED") ? atoi(getenv("MMRCA_ATTN_BWD_FUSED")) : 3;
-  static const int bwd_prefetch = getenv("MMRCA_ATTN_BWD_PREFETCH") ? atoi(getenv("MMRCA_ATTN_BWD_PREFETCH")) : 1;      // A/B switch of the first-tile fragment prefetch
-  if (use_v && bwd_fused == 3 && S <= 16 * 13) {
+  const bool vit = nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12;      // the ViT's attention
+  if (vit && S <= 16 * 13) {
     // persistent 8-wave workgroups (two tiles per wave), six image slots: every operand crosses the fabric once
-    static int ncu_b = 0;
-    if (ncu_b == 0) {
-      int dev = 0, n = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-      ncu_b = n;
-    }
     const int nbh = B * H;
-    const int grid = nbh < ncu_b ? nbh : ncu_b;
+    const int grid = nbh < attn_cu_count() ? nbh : attn_cu_count();
     const int ldp = 2 * 14 * 16 * 4 + 6 * 13 * 16 * 128 + 2048;
     MMRCA_MAX_LDS(ldp, mha_bwd_p_mfma_v_k<14, 8, 2>);
     hipLaunchKernelGGL((mha_bwd_p_mfma_v_k<14, 8, 2>), dim3(grid), dim3(512), ldp, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
@@ -1924,31 +1638,12 @@ int mmrca_mha_bwd_mfma(const void* qkv, const int32_t* key_mask, const void* out
     MMRCA_CHECK_LAUNCH("mha_bwd(mfma,persistent)");
     return 0;
   }
-  if (use_v && (bwd_fused == 1 || bwd_fused == 3)) {     // one launch, two workgroups per CU: the Q | dO and K | V images time-share 56 KiB
+  if (vit) {     // S in (208, 224]: one launch, two workgroups per CU: the Q | dO and K | V images time-share 56 KiB
     const int ldf = 2 * 14 * 16 * 128 + STAT_EXTRA(14);
-    MMRCA_MAX_LDS(ldf, mha_bwd_fused_mfma_v_k<14, 8, true>);
-    hipLaunchKernelGGL((mha_bwd_fused_mfma_v_k<14, 8, true>), dim3(B * H), dim3(512), ldf, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                       (bf16_t*)dqkv, H, S, scale, g_attn_stamps, bwd_prefetch);
+    MMRCA_MAX_LDS(ldf, mha_bwd_fused_mfma_v_k<14, 8>);
+    hipLaunchKernelGGL((mha_bwd_fused_mfma_v_k<14, 8>), dim3(B * H), dim3(512), ldf, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
+                       (bf16_t*)dqkv, H, S, scale, g_attn_stamps);
     MMRCA_CHECK_LAUNCH("mha_bwd(mfma,fused)");
-    return 0;
-  }
-  if (use_v && bwd_fused == 2) {     // one launch, one 16-wave workgroup per CU: all four operand images staged once per (b, h)
-    const int ldf = 4 * 14 * 16 * 128 + STAT_EXTRA(14);
-    MMRCA_MAX_LDS(ldf, mha_bwd_fused_mfma_v_k<14, 16, false>);
-    hipLaunchKernelGGL((mha_bwd_fused_mfma_v_k<14, 16, false>), dim3(B * H), dim3(1024), ldf, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                       (bf16_t*)dqkv, H, S, scale, g_attn_stamps, bwd_prefetch);
-    MMRCA_CHECK_LAUNCH("mha_bwd(mfma,fused16)");
-    return 0;
-  }
-  if (use_v) {
-    const int ldq = 2 * 14 * 16 * 128, ldkv = 2 * 14 * 16 * 128 + STAT_EXTRA(14);
-    MMRCA_MAX_LDS(ldq, mha_bwd_dq_mfma_v_k<14, 8>);
-    hipLaunchKernelGGL((mha_bwd_dq_mfma_v_k<14, 8>), dim3(B * H), dim3(512), ldq, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                       (bf16_t*)dqkv, H, S, scale);
-    MMRCA_MAX_LDS(ldkv, mha_bwd_dkv_mfma_v_k<14, 8>);
-    hipLaunchKernelGGL((mha_bwd_dkv_mfma_v_k<14, 8>), dim3(B * H), dim3(512), ldkv, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
-                       (bf16_t*)dqkv, H, S, scale);
-    MMRCA_CHECK_LAUNCH("mha_bwd(mfma,v)");
     return 0;
   }
   AT_SWITCH(K_DQ, BIAS_EXTRA, true, true, true, (const bf16_t*)qkv, key_mask, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, H, S, scale, drop_p, drop_seed, cu);

@@ -3,7 +3,6 @@
 // phase and head-dim channels for the value phase; probabilities cross over through LDS.  This is the fp32
 // "parity mode" kernel and the checker for the MFMA kernel in attention_mfma.hip; it is not the fast path.
 #include "common.h"
-#include <stdlib.h>
 
 #define ATT_MAX_S 1024
 #define ATT_MAX_DH 128
@@ -359,13 +358,12 @@ mha_bwd_dkv_lds_k(const T* __restrict__ qkv, const int32_t* __restrict__ key_mas
 static size_t atl_bytes(int S, int dh, int per_wave_floats, int extra_floats) {
   return ((size_t)2 * S * (dh + 1) + extra_floats + (size_t)ATL_WAVES * per_wave_floats) * sizeof(float);
 }
-static const bool g_att_lds = !(getenv("MMRCA_ATTN_REF_LDS") && atoi(getenv("MMRCA_ATTN_REF_LDS")) == 0);
 
 int mmrca_mha_fwd_ref(const void* qkv, const int32_t* key_mask, void* out, float* lse, int B, int H, int S, int dh,
                       float scale, float drop_p, uint64_t drop_seed, const int32_t* cu, int dtype, hipStream_t st) {
   MMRCA_REQUIRE(S <= ATT_MAX_S && dh <= ATT_MAX_DH && dh % 4 == 0, "mha_fwd(ref): S=%d dh=%d unsupported", S, dh);
   const size_t ldsl = atl_bytes(S, dh, ATT_MAX_DH + S, 0);
-  if (g_att_lds && ldsl <= 160 * 1024) {
+  if (ldsl <= 160 * 1024) {
     MMRCA_DISPATCH_DTYPE(dtype, "mha_fwd",
       MMRCA_MAX_LDS((int)ldsl, mha_fwd_lds_k<T>);
       hipLaunchKernelGGL(mha_fwd_lds_k<T>, dim3(B * H), dim3(64 * ATL_WAVES), ldsl, st, (const T*)qkv, key_mask, (T*)out, lse, B, H, S, dh, scale, drop_p, drop_seed, cu);)
@@ -385,7 +383,7 @@ int mmrca_mha_bwd_ref(const void* qkv, const int32_t* key_mask, const void* out,
                       int dtype, hipStream_t st) {
   MMRCA_REQUIRE(S <= ATT_MAX_S && dh <= ATT_MAX_DH && dh % 4 == 0, "mha_bwd(ref): S=%d dh=%d unsupported", S, dh);
   const size_t ll1 = atl_bytes(S, dh, 2 * ATT_MAX_DH + S, 0), ll2 = atl_bytes(S, dh, 2 * ATT_MAX_DH + 2 * S, S);
-  if (g_att_lds && ll1 <= 160 * 1024 && ll2 <= 160 * 1024) {
+  if (ll1 <= 160 * 1024 && ll2 <= 160 * 1024) {
     MMRCA_DISPATCH_DTYPE(dtype, "mha_bwd",
       MMRCA_MAX_LDS((int)ll1, mha_bwd_dq_lds_k<T>);
       MMRCA_MAX_LDS((int)ll2, mha_bwd_dkv_lds_k<T>);

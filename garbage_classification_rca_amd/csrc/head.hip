@@ -18,7 +18,6 @@
 // tiles per wave, 4 waves of a workgroup splitting 256 rows and reducing in LDS, one atomic per address per 256 rows)
 // instead of one atomic per weight per SAMPLE (24 M atomics at B=256) as the first version did.
 #include "common.h"
-#include <stdlib.h>
 
 #define HP 16          // pseudo-patches (multimodal_model.py:250)
 #define SA_HID 128
@@ -53,7 +52,7 @@ struct AttnG { float *wq, *bq, *wk, *bk, *wv, *bv, *g, *b; };
 #define G_FLOATS (G_DS + 256)
 #define MISC_FLOATS 256             // red[16] | norms[2] | pad | dl[16] @32 | part[16*8] @64
 
-struct HeadDims { int d_img, d_txt, pi, pt, wfull, n_classes, mode, reverse, stop; };   // stop: timing ablation only (MMRCA_HEAD_STOP)
+struct HeadDims { int d_img, d_txt, pi, pt, wfull, n_classes, mode, reverse; };
 
 // LDS plan, offsets in floats
 struct HeadLayout {
@@ -505,7 +504,6 @@ head_fwd_k(const T* __restrict__ img, const T* __restrict__ txt, MmrcaHeadWeight
   }
 }
 
-#define STOP(n) if (d.stop == (n)) return
 template <typename T>
 __global__ void __launch_bounds__(HEAD_THREADS)
 head_bwd_k(const float* __restrict__ dlogits, const T* __restrict__ img, const T* __restrict__ txt, MmrcaHeadWeights w,
@@ -530,7 +528,7 @@ head_bwd_k(const float* __restrict__ dlogits, const T* __restrict__ img, const T
     }
   }
   if (t < d.n_classes) { const float v = dlogits[b * d.n_classes + t]; dl[t] = v; atomicAdd(gw.fin_b + t, v); }
-  __syncthreads(); STOP(1);
+  __syncthreads();
   // classifier backward (dropout mask regenerated from the counter); v = dropped input goes to the workspace
   int c0, c1, woff; active_cols(d, c0, c1, woff);
   const int wact = c1 - c0;
@@ -544,7 +542,7 @@ head_bwd_k(const float* __restrict__ dlogits, const T* __restrict__ img, const T
     }
     if (c < CA_FLAT) hs[L.doc + c] = gsum; else dxs[c - CA_FLAT] = gsum;
   }
-  __syncthreads(); STOP(2);
+  __syncthreads();
   if (d.mode != 1) {           // features_only never sees the attention blocks: their gradients stay zero
     float* ws = hs + L.ws + side * WS_FLOATS;
     float* G = hs + L.g + side * G_FLOATS;
@@ -557,29 +555,29 @@ head_bwd_k(const float* __restrict__ dlogits, const T* __restrict__ img, const T
     // ---- cross stage
     const AttnG gca = grad_block(gw, 1, side);
     if (gwave == 0) attn_bwd_core<CA_HID, CA_OUT>(ws, G, hb.ca, gca, d.reverse, hs + L.doc + side * (HP * CA_OUT), lane);
-    __syncthreads(); STOP(3);
+    __syncthreads();
     for (int k = t; k < 2 * SA_FLAT; k += HEAD_THREADS) dosa[k] = 0.f;
     attn_bwd_qkv<CA_HID, CA_OUT>(ws, G, d.reverse, sc.dq_ca[side] + row0 * CA_HID, CA_HID, sc.dkv_ca[side] + row0 * CA_DKV, CA_DKV,
                                  sc.dkv_ca[side] + row0 * CA_DKV + CA_HID, CA_DKV, gwave, lane);
-    __syncthreads(); STOP(4);
+    __syncthreads();
     // queries came from the own side's self-attention output, keys/values from the other side's
     attn_bwd_dx<CA_HID, CA_OUT>(G, hb.ca, SA_OUT, dosa + side * SA_FLAT, 1, gwave, lane);
-    __syncthreads(); STOP(5);             // the other side's key/value gradient lands in the same array
+    __syncthreads();             // the other side's key/value gradient lands in the same array
     attn_bwd_dx<CA_HID, CA_OUT>(G, hb.ca, SA_OUT, dosa + (1 - side) * SA_FLAT, 2, gwave, lane);
-    __syncthreads(); STOP(6);
+    __syncthreads();
     // ---- self stage: recompute its forward into the (now free) workspace, then differentiate
     proj_self(xm, pm, hb.sa, ws, gwave, lane);
-    __syncthreads(); STOP(7);
+    __syncthreads();
     if (gwave == 0) {
       attn_core<SA_HID, SA_OUT, true>(ws, hb.sa, false, osa_own, lane);
       attn_bwd_core<SA_HID, SA_OUT>(ws, G, hb.sa, grad_block(gw, 0, side), false, dosa + side * SA_FLAT, lane);
     }
-    __syncthreads(); STOP(8);
+    __syncthreads();
     float* gy = sc.dy_sa[side] + row0 * SA_DY;
     attn_bwd_qkv<SA_HID, SA_OUT>(ws, G, false, gy, SA_DY, gy + SA_HID, SA_DY, gy + 2 * SA_HID, SA_DY, gwave, lane);
-    __syncthreads(); STOP(9);
+    __syncthreads();
     attn_bwd_dx<SA_HID, SA_OUT>(G, hb.sa, pm, dxm, 3, gwave, lane);
-    __syncthreads(); STOP(10);
+    __syncthreads();
   }
   // y = x/||x||  ->  dx = (dy - y (y.dy)) / ||x||
   {
@@ -591,7 +589,7 @@ head_bwd_k(const float* __restrict__ dlogits, const T* __restrict__ img, const T
     for (int k = gt; k < n; k += 256) dot += y[k] * dy[k];
     dot = wave_sum(dot);
     if (lane == 0) misc[side * 4 + gwave] = dot;
-    __syncthreads(); STOP(11);
+    __syncthreads();
     const float tot = misc[side * 4] + misc[side * 4 + 1] + misc[side * 4 + 2] + misc[side * 4 + 3];
     const float inv = 1.f / misc[16 + side];
     if (dst) for (int k = gt; k < n; k += 256) dst[b * n + k] = from_f<T>((dy[k] - y[k] * tot) * inv);
@@ -747,7 +745,7 @@ extern "C" int mmrca_head_fwd(const void* img, const void* txt, const MmrcaHeadW
   if (int rc = head_check(B, d_img, d_txt, n_classes, mode)) return rc;
   MMRCA_REQUIRE(head_weights_ok(w), "head_fwd: null weight pointer");
   MMRCA_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "head_fwd: dropout p must be in [0,1)");
-  HeadDims d = {d_img, d_txt, d_img / HP, d_txt / HP, CA_FLAT + d_img + d_txt, n_classes, mode, reverse ? 1 : 0, 0};
+  HeadDims d = {d_img, d_txt, d_img / HP, d_txt / HP, CA_FLAT + d_img + d_txt, n_classes, mode, reverse ? 1 : 0};
   const HeadLayout L = head_layout(d, false);
   const size_t lds = (size_t)L.total * 4;
   MMRCA_REQUIRE(lds <= 160 * 1024, "head_fwd: LDS budget exceeded");
@@ -777,8 +775,7 @@ extern "C" int mmrca_head_bwd(const float* dlogits, const void* img, const void*
   }
   MMRCA_REQUIRE(workspace && workspace_bytes >= mmrca_head_bwd_workspace_bytes(B, d_img, d_txt) && ((uintptr_t)workspace & 15) == 0,
                 "head_bwd: workspace of mmrca_head_bwd_workspace_bytes() bytes (16-byte aligned) required");
-  static const int head_stop = getenv("MMRCA_HEAD_STOP") ? atoi(getenv("MMRCA_HEAD_STOP")) : 0;
-  HeadDims d = {d_img, d_txt, d_img / HP, d_txt / HP, CA_FLAT + d_img + d_txt, n_classes, mode, reverse ? 1 : 0, head_stop % 100};
+  HeadDims d = {d_img, d_txt, d_img / HP, d_txt / HP, CA_FLAT + d_img + d_txt, n_classes, mode, reverse ? 1 : 0};
   const HeadLayout L = head_layout(d, true);
   const size_t lds = (size_t)L.total * 4;
   MMRCA_REQUIRE(lds <= 160 * 1024, "head_bwd: LDS budget exceeded");
@@ -814,7 +811,6 @@ extern "C" int mmrca_head_bwd(const float* dlogits, const void* img, const void*
   MMRCA_REQUIRE(p.n_blocks == (mode != 1 ? wg_blocks(d_img, d_txt) : 0) && p.n_blocks <= 64 && p.ksplit == wg_ksplit(B), "head_bwd: block plan mismatch");
   const int fin_blocks = p.fin_colblocks * ((B + FIN_CHUNK - 1) / FIN_CHUNK);
   const int grid = p.n_blocks * p.ksplit + fin_blocks;
-  if (head_stop >= 100) return 0;
   MMRCA_MAX_LDS(65536, head_wgrad_k);
   hipLaunchKernelGGL(head_wgrad_k, dim3(grid), dim3(256), 65536, (hipStream_t)stream, p);
   MMRCA_CHECK_LAUNCH("head_wgrad");

@@ -3,7 +3,6 @@
 // per row, 8- or 16-byte accesses per lane, fp32 statistics, wave-shuffle reductions.
 #include "common.h"
 #include <type_traits>
-#include <stdlib.h>
 
 #define LN_MAXV 8   // row kept in registers: D <= 256 * LN_MAXV
 
@@ -224,9 +223,8 @@ static int add_layernorm_fwd_impl(const void* x, const void* res, const void* ga
       else { if (drop) LN_FWD16(NV2_, RP_, false, true); else LN_FWD16(NV2_, RP_, false, false); }                           \
     } while (0)
     const int nv2 = (D + 511) / 512;
-    // packed rows whenever the normalised values are bf16 numbers anyway (see the kernel); MMRCA_LN_PACK=0: the fp32-row form
-    static const bool pack_on = !(getenv("MMRCA_LN_PACK") && atoi(getenv("MMRCA_LN_PACK")) == 0);
-    const bool pack = pack_on && (sum_out || (!res && in_drop_p == 0.f));
+    // packed rows whenever the normalised values are bf16 numbers anyway (see the kernel); the fp32-row form otherwise
+    const bool pack = sum_out || (!res && in_drop_p == 0.f);
     const bool drop = in_drop_p > 0.f || out_drop_p > 0.f;
     if (nv2 <= 1) LN_FWD16_PD(1, 2); else if (nv2 == 2) LN_FWD16_PD(2, 2); else LN_FWD16_PD(3, 1);      // 3: BLIP-2's ViT-g rows (D = 1408)
 #undef LN_FWD16_PD
@@ -512,7 +510,7 @@ extern "C" int mmrca_layernorm_bwd(const void* dy, const void* s, const void* ga
   MMRCA_REQUIRE(ld_dy >= D && ld_s >= D && ld_ds >= D && ld_dy % 4 == 0 && ld_s % 4 == 0 && ld_ds % 4 == 0, "layernorm_bwd: bad leading dims");
   if (rows <= 0) return 0;
   int64_t want = (rows + 3) / 4;
-  static const int ln_bwd_grid = getenv("MMRCA_LN_BWD_GRID") ? atoi(getenv("MMRCA_LN_BWD_GRID")) : 256;       // blocks of the bf16 fast path (LNB_WAVES waves each): one per CU
+  constexpr int ln_bwd_grid = 256;       // blocks of the bf16 fast path (LNB_WAVES waves each): one per CU
   const int grid = (int)(want < 1024 ? want : 1024);
   const int64_t want16 = (rows + LNB_WAVES - 1) / LNB_WAVES;
   const int grid16 = (int)(want16 < ln_bwd_grid ? want16 : ln_bwd_grid);

@@ -416,7 +416,7 @@ def mha_fwd(qkv, key_mask, out, lse, B, H, S, dh, scale, dtype, impl=IMPL_AUTO, 
 
 
 def mha_fwd_planes_ok(S, dh):
-    return dh == 64 and 1 <= S <= 208 and os.environ.get("MMRCA_ATTN_F32_MFMA", "1") != "0"
+    return dh == 64 and 1 <= S <= 208
 
 
 def mha_fwd_planes(qkv, key_mask, out, out_planes, lse, B, H, S, dh, scale, drop_p=0.0, drop_seed=0, cu=None):
@@ -437,7 +437,7 @@ def mha_fwd_planes_in(qkv_planes, key_mask, out, out_planes, lse, B, H, S, dh, s
 
 
 def mha_fwd_x3_ok(S, dh):
-    return dh == 64 and 1 <= S <= 224 and os.environ.get("MMRCA_ATTN_X3", "1") != "0"
+    return dh == 64 and 1 <= S <= 224
 
 
 def mha_fwd_x3(qkv_planes, key_mask, out_planes, lse, B, H, S, dh, scale, drop_p=0.0, drop_seed=0, cu=None):

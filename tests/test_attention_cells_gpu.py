@@ -2,7 +2,7 @@
 path falls to above S = 208, and the class-token kernels of attention_cls.hip) against a float64 statement of the same
 operation on the kernel's exact inputs -- forward AND backward, checked per (sequence, head) block and per row of each of
 out, dQ, dK and dV, so that a failure names the cell, the head and the segment that broke.  Needs an MI355X; every call
-goes through the C ABI with the shipped defaults (the MMRCA_ATTN_* A/B switches are out of scope).
+goes through the C ABI.
 
 Inputs are built to expose what randn hides: peaky scores (one dominant key per row), masked keys whose scores sit ~100
 above every valid score and whose V rows are large (a masked key that enters the row maximum or P.V shows at once), and
@@ -76,31 +76,31 @@ def cell(S, dtype, masked, packed, drop, nbh, cls=False, ncu=None):
     if cls:                                                     # attention_cls.hip:176, 189 (any dtype, S <= 1024)
         return (f"mha_cls_fwd_k<{tn}>", f"mha_cls_bwd_k<{tn}>")
     if dtype == "bf16":                                         # attention_api.hip:23, 77: bf16, head dim 64, S <= 512 -> MFMA
-        nkt = next(o for o in (2, 4, 8, 14, 16, 32) if o >= (S + 31) // 32 * 2)        # attention_mfma.hip:1374 pick_nkt
-        vit = nkt == 14 and not drop and not masked and not packed and S > 16 * 12      # attention_mfma.hip:1830, 1904
+        nkt = next(o for o in (2, 4, 8, 14, 16, 32) if o >= (S + 31) // 32 * 2)        # attention_mfma.hip pick_nkt
+        vit = nkt == 14 and not drop and not masked and not packed and S > 16 * 12      # mmrca_mha_fwd_mfma, mmrca_mha_bwd_mfma
         if vit:
-            fwd = f"mha_fwd_mfma_p_k<14,16>[{_walk(nbh, ncu)}]"                         # attention_mfma.hip:1830-1838
-            if S <= 16 * 13:                                                            # attention_mfma.hip:1909-1925
+            fwd = f"mha_fwd_mfma_p_k<14,16>[{_walk(nbh, ncu)}]"                         # mmrca_mha_fwd_mfma
+            if S <= 16 * 13:                                                            # mmrca_mha_bwd_mfma
                 return (fwd, f"mha_bwd_p_mfma_v_k<14,8,2>[{_walk(nbh, ncu)}]")
-            return (fwd, "mha_bwd_fused_mfma_v_k<14,8,true>")                         # attention_mfma.hip:1927-1933
-        # AT_SWITCH (attention_mfma.hip:1406-1414): nkt 2/4/8 run 4 waves; 14/16 run 8 where the call passes W8_PLAIN / W8_DROP,
-        # 32 only where it also passes W8_32.  The forward passes (true, false, false) (:1849), dQ (true, true, true) (:1954),
-        # dK/dV (true, false, true) (:1955).
+            return (fwd, "mha_bwd_fused_mfma_v_k<14,8>")                              # mmrca_mha_bwd_mfma
+        # AT_SWITCH (attention_mfma.hip): nkt 2/4/8 run 4 waves; 14/16 run 8 where the call passes W8_PLAIN / W8_DROP,
+        # 32 only where it also passes W8_32.  The forward passes (true, false, false) (mmrca_mha_fwd_mfma), dQ (true, true, true)
+        # and dK/dV (true, false, true) (mmrca_mha_bwd_mfma).
         def waves(w8_plain, w8_drop, w8_32):
             if nkt <= 8:
                 return 4
             w8 = w8_drop if drop else w8_plain
             return 8 if (w8 and (nkt != 32 or w8_32)) else 4
         d = "true" if drop else "false"
-        return (f"mha_fwd_mfma_k<{nkt},{d},{waves(True, False, False)},1>",
+        return (f"mha_fwd_mfma_k<{nkt},{d},{waves(True, False, False)}>",
                 f"mha_bwd_dq_mfma_k<{nkt},{d},{waves(True, True, True)}>",
                 f"mha_bwd_dkv_mfma_k<{nkt},{d},{waves(True, False, True)}>")
     d = "true" if drop else "false"
-    if S <= 208:                                                # attention_f32.hip:346 mmrca_mha_f32m_ok; attention_api.hip:25, 79
-        nkt = 4 if S <= 64 else (8 if S <= 128 else 13)         # attention_f32.hip:350 nkt_for, launched at :366-368
-        return (f"mha_fwd_f32m_k<{nkt},{d}>", f"mha_bwd_dq_f32m_k<{d}>", f"mha_bwd_dkv_f32m_k<{d}>")   # :378-390 (ceil(S/16) tiles)
-    # attention_api.hip:26, 81 -> attention_ref.hip: the LDS-staged kernels while their images fit 160 KiB (:368, :388), else the
-    # row-per-wave kernels.  Sizes as atl_bytes (:358) with ATT_MAX_DH = 128, ATL_WAVES = 16.
+    if S <= 208:                                                # attention_f32.hip mmrca_mha_f32m_ok; attention_api.hip:25, 79
+        nkt = 4 if S <= 64 else (8 if S <= 128 else 13)         # attention_f32.hip nkt_for, mmrca_mha_fwd_f32m
+        return (f"mha_fwd_f32m_k<{nkt},{d}>", f"mha_bwd_dq_f32m_k<{d}>", f"mha_bwd_dkv_f32m_k<{d}>")   # mmrca_mha_bwd_f32m (ceil(S/16) tiles)
+    # attention_api.hip:26, 81 -> attention_ref.hip: the LDS-staged kernels while their images fit 160 KiB (mmrca_mha_fwd_ref,
+    # mmrca_mha_bwd_ref), else the row-per-wave kernels.  Sizes as atl_bytes with ATT_MAX_DH = 128, ATL_WAVES = 16.
     def atl(per_wave, extra):
         return (2 * S * (DH + 1) + extra + 16 * per_wave) * 4
     fwd = "mha_fwd_lds_k<float>" if atl(128 + S, 0) <= 160 * 1024 else "mha_fwd_ref_k<float>"

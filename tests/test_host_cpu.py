@@ -839,6 +839,20 @@ def test_split_phase_asm_loads_are_not_touched_before_their_wait():
     assert alloc and all(v >= 252 for v in alloc.values()), alloc
 
 
+def test_no_kernel_source_reads_the_environment():
+    """the kernel sources carry no A/B switches: nothing under csrc/ calls getenv, and the only MMRCA_* variable lib.py reads is
+    MMRCA_SK (include/mmrca.h documents it)"""
+    pkg = os.path.join(ROOT, "garbage_classification_rca_amd")
+    for f in sorted(os.listdir(os.path.join(pkg, "csrc"))):
+        if f.endswith((".hip", ".cpp", ".h")):
+            with open(os.path.join(pkg, "csrc", f)) as fh:
+                for n, line in enumerate(fh, 1):
+                    assert "getenv" not in line, f"csrc/{f}:{n}: {line.strip()}"
+    with open(os.path.join(pkg, "lib.py")) as fh:
+        reads = re.findall(r"os\.environ\s*(?:\.get\s*\(|\[)\s*[\"'](MMRCA_[A-Z0-9_]+)", fh.read())
+    assert set(reads) == {"MMRCA_SK"}, reads
+
+
 def test_bench_launches_its_own_ranks_and_reports_a_failed_one(tmp_path, capfd):
     """bench.launch_ranks (python bench.py --gpus N with no torchrun around it; main_both.py:386-388's multi-GPU entry): every child gets
     torchrun's environment, rank 0's stdout is the parent's, and one failing rank ends the others and sets the exit code.  The children

@@ -1,8 +1,7 @@
 """Every dispatch cell of the LayerNorm kernels in csrc/rowops.hip (add_ln_fwd_bf16_k, add_ln_fwd_k with and without the bf16x3
 planes, ln_bwd_bf16_k with an fp32 or bf16 saved sum, ln_bwd_k) against a float64 statement of the same operation on the kernel's
 exact inputs, and the rest of rowops.hip (GELU backward, column sums, embeddings, patchify, ViT assembly, loss, optimizers, casts,
-stochastic-depth scales) against float64 or bitwise.  Needs an MI355X; every call goes through the C ABI with the shipped defaults
-(MMRCA_LN_PACK and MMRCA_LN_BWD_GRID are read once per process and are out of scope).
+stochastic-depth scales) against float64 or bitwise.  Needs an MI355X; every call goes through the C ABI.
 
 Inputs are built to expose what randn hides: rows with a large common offset (|mean| >> std: a one-pass variance or a dropped
 centring shows), rows of near-constant values (rstd near 1/sqrt(eps)), gamma and beta of mixed signs, and loud finite values in
@@ -125,28 +124,28 @@ def cell(c):
     D, R, bf = c.D, max(c.rows, 0), c.dtype == "bf16"
     t = "bf16" if bf else "float"
     if c.op in ("fwd", "x3"):
-        fast = (c.op == "fwd" and bf and D % 8 == 0 and D <= 1536 and all(ld % 8 == 0 for ld in c.lds)   # :214-215
+        fast = (c.op == "fwd" and bf and D % 8 == 0 and D <= 1536 and all(ld % 8 == 0 for ld in c.lds)   # :213-214
                 and not c.mis)
         if fast:
-            nv2 = _cdiv(D, 512)                                            # :226
-            rp = 2 if nv2 <= 2 else 1                                      # :231
-            pack = c.sum_out or (not c.res and c.in_p == 0)                # :229
-            drop = c.in_p > 0 or c.out_p > 0                               # :230
-            return f"add_ln_fwd_bf16_k<{nv2},{rp},{_tf(pack)},{_tf(drop)}>", 4 * min(_cdiv(R, 8), 1024) * rp   # :216, :126
-        nv = _cdiv(D, 256)                                                 # :242
-        nv = nv if nv <= 4 else 8                                          # :244-245
-        planes = "[y_hi,y_lo]" if c.op == "x3" else ""                     # :262-268 (fp32 only, :210)
-        return f"add_ln_fwd_k<{t},{nv}>{planes}", 4 * min(_cdiv(R, 4), 4096)                                 # :237
+            nv2 = _cdiv(D, 512)                                            # :225
+            rp = 2 if nv2 <= 2 else 1                                      # :229
+            pack = c.sum_out or (not c.res and c.in_p == 0)                # :227
+            drop = c.in_p > 0 or c.out_p > 0                               # :228
+            return f"add_ln_fwd_bf16_k<{nv2},{rp},{_tf(pack)},{_tf(drop)}>", 4 * min(_cdiv(R, 8), 1024) * rp   # :215, :125
+        nv = _cdiv(D, 256)                                                 # :240
+        nv = nv if nv <= 4 else 8                                          # :242-243
+        planes = "[y_hi,y_lo]" if c.op == "x3" else ""                     # :260-266 (fp32 only, :209)
+        return f"add_ln_fwd_k<{t},{nv}>{planes}", 4 * min(_cdiv(R, 4), 4096)                                 # :235
     if c.op == "bwd":
-        fast = (bf and D % 8 == 0 and D <= 1024 and all(ld % 8 == 0 for ld in c.lds) and not c.mis)         # :520-522
+        fast = (bf and D % 8 == 0 and D <= 1024 and all(ld % 8 == 0 for ld in c.lds) and not c.mis)         # :518-520
         if fast:
-            nv2 = 1 if _cdiv(D, 512) <= 1 else 2                           # :531-532
-            return f"ln_bwd_bf16_k<{nv2},{_tf(c.dcol)},{_tf(c.dbranch)}>", 8 * min(_cdiv(R, 8), 256)          # :517-518, :529
-        nv = _cdiv(D, 256)                                                 # :542
-        nv = nv if nv <= 4 else 8                                          # :544-545
-        return f"ln_bwd_k<{t},{nv}>", 4 * min(_cdiv(R, 4), 1024)                                            # :514-516
-    nv2 = 1 if D <= 512 else 2                                             # :576
-    return f"ln_bwd_bf16_k<{nv2},{_tf(c.dcol)},{_tf(c.dbranch)},true>", 8 * min(_cdiv(R, 8), 256)            # :566-567, :574
+            nv2 = 1 if _cdiv(D, 512) <= 1 else 2                           # :529-530
+            return f"ln_bwd_bf16_k<{nv2},{_tf(c.dcol)},{_tf(c.dbranch)}>", 8 * min(_cdiv(R, 8), 256)          # :515-516, :527
+        nv = _cdiv(D, 256)                                                 # :540
+        nv = nv if nv <= 4 else 8                                          # :542-543
+        return f"ln_bwd_k<{t},{nv}>", 4 * min(_cdiv(R, 4), 1024)                                            # :512-514
+    nv2 = 1 if D <= 512 else 2                                             # :574
+    return f"ln_bwd_bf16_k<{nv2},{_tf(c.dcol)},{_tf(c.dbranch)},true>", 8 * min(_cdiv(R, 8), 256)            # :564-565, :572
 
 
 def all_cells():
@@ -635,14 +634,15 @@ def test_the_restated_dispatch_matches_rowops_source():
               "if (dtype == MMRCA_BF16 && D % 8 == 0 && D <= 1536 && ld_x % 8 == 0 && ld_y % 8 == 0 && aligned16p(x) && aligned16p(y)",
               "const int g2 = (int)((rows + 7) / 8 < 1024 ? (rows + 7) / 8 : 1024);",
               "const int nv2 = (D + 511) / 512;",
-              "const bool pack = pack_on && (sum_out || (!res && in_drop_p == 0.f));",
+              "const bool pack = sum_out || (!res && in_drop_p == 0.f);",
               "const bool drop = in_drop_p > 0.f || out_drop_p > 0.f;",
               "if (nv2 <= 1) LN_FWD16_PD(1, 2); else if (nv2 == 2) LN_FWD16_PD(2, 2); else LN_FWD16_PD(3, 1);",
               "const int grid = (int)((rows + 3) / 4 < 4096 ? (rows + 3) / 4 : 4096);",
               "const int nv = (D + 255) / 256;",
               "if (nv <= 1) LN_FWD_LAUNCH(1); else if (nv <= 2) LN_FWD_LAUNCH(2); else if (nv <= 3) LN_FWD_LAUNCH(3); "
               "else if (nv <= 4) LN_FWD_LAUNCH(4); else LN_FWD_LAUNCH(8);",
-              "atoi(getenv(\"MMRCA_LN_BWD_GRID\")) : 256;",
+              "constexpr int ln_bwd_grid = 256;",
+              "const int grid16 = (int)(want16 < ln_bwd_grid ? want16 : ln_bwd_grid);",
               "const int grid = (int)(want < 1024 ? want : 1024);",
               "const int64_t want16 = (rows + LNB_WAVES - 1) / LNB_WAVES;",
               "if (dtype == MMRCA_BF16 && D % 8 == 0 && D <= 1024 && ld_dy % 8 == 0 && ld_s % 8 == 0 && ld_ds % 8 == 0 && dgamma && dbeta",

@@ -1,10 +1,14 @@
 #!/usr/bin/env python
-"""Timing of the fused attention kernels on the cfg-2 shapes (B=256: ViT 12 heads x 197 tokens; DistilBERT 12 x 64)."""
+"""Timing of the fused attention kernels on the cfg-2 shapes (B=256: ViT 12 heads x 197 tokens; DistilBERT 12 x 64).
+An optional argument replaces the ViT's sequence length (224 times the fused backward of S in (208, 224]); the text shape is then skipped."""
 import sys, os, math, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from garbage_classification_rca_amd import lib as L
 L.load()
-for name, B, H, S, masked in (("vit", 256, 12, 197, False), ("text", 256, 12, 64, True)):
+SHAPES = (("vit", 256, 12, 197, False), ("text", 256, 12, 64, True))
+if len(sys.argv) > 1:
+    SHAPES = (("vit", 256, 12, int(sys.argv[1]), False),)
+for name, B, H, S, masked in SHAPES:
     dh = 64
     qkv = torch.randn(B * S, 3 * H * dh, device="cuda").bfloat16()
     out = torch.empty(B * S, H * dh, device="cuda", dtype=torch.bfloat16)
