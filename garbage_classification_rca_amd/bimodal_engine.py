@@ -23,18 +23,17 @@ is the reference's behaviour and it is reproduced here; under data parallelism e
 batch.  ``drop_p`` of ``forward`` is the probability of dropout1 and dropout2 (the module passes the reference's fixed 0.86 in train
 mode; ``--model_dropout`` has no effect on this forward, and ``gru_bimodal``'s ``dropout=0.35`` none on a single layer).
 
-Same ``forward`` / ``backward`` / ``trainable_spans`` / ``groups`` contract as the MM-RCA engine, so the flat optimizers, ``GradSync``,
-``hip_train_step`` and ``GraphedTrainStep`` drive it unchanged.
+``forward`` / ``backward`` / ``trainable_spans`` / ``groups`` ARE the MM-RCA engine's (constructor, two-stream encoders and step
+preamble inherited); this class supplies the head through the hooks ``_head_entries``, ``_head_forward`` and ``_head_grads``.  So the
+flat optimizers, ``GradSync``, ``hip_train_step`` and ``GraphedTrainStep`` drive it unchanged.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional
-
 import torch
 
 from . import lib as L
-from .engine import MMRCAEngine, TextPack
+from .engine import MMRCAEngine
 
 BIMODAL_DIM, BIMODAL_HIDDEN, BIMODAL_PROJ, BIMODAL_CLASSES = 400, 500, 450, 4      # multimodal_model.py:302-305 (num_classes = 4 is hard-coded)
 BIMODAL_DROPOUT = 0.86                                                              # dropout1 / dropout2, whatever --model_dropout says
@@ -47,7 +46,10 @@ def _gru_entries(name, n_in, hid):
 
 
 class BimodalEngine(MMRCAEngine):
-    """Owns parameters, gradients and activations of one bimodal-fusion replica on one GPU."""
+    """Owns parameters, gradients and activations of one bimodal-fusion replica on one GPU.  ``forward`` / ``backward`` are the base
+    engine's: the two-stream encoders around this class's ``_head_forward`` / ``_head_grads``."""
+
+    PATH_NAME = "bimodal"
 
     def __init__(self, text_model: str, image_model: str = "eff_v2_medium", n_classes: int = 4, dtype="bf16x3f", device="cuda",
                  image_size: int = 480, gemm_impl: int = L.IMPL_AUTO, attn_impl: int = L.IMPL_AUTO):
@@ -93,7 +95,10 @@ class BimodalEngine(MMRCAEngine):
         return self.buf("bim_" + name, rows, cols, torch.float32)
 
     def _head_forward(self, cls, feat, B, drop_p, seeds):
-        """cls [B, d_txt], feat [B, d_img] in the encoders' dtypes -> logits fp32 [B, 4]; keeps what the backward reads"""
+        """cls [B, d_txt], feat [B, d_img] in the encoders' dtypes -> logits fp32 [B, 4]; keeps what the backward reads.  drop_p:
+        dropout1's and dropout2's probability, seeds: their two mask seeds.  Row b of the batch is time step b of the three GRUs."""
+        if not 0.0 <= drop_p < 1.0:
+            raise ValueError(f"drop_p must be in [0, 1), got {drop_p}")
         A, D, Hh, P = self.arena.view, BIMODAL_DIM, BIMODAL_HIDDEN, BIMODAL_PROJ
         dt, di = self.d_txt, self.d_img
         ld, so = dt + di, [0, dt, dt + di]
@@ -126,7 +131,7 @@ class BimodalEngine(MMRCAEngine):
         L.dropout_f32(h2, P, proj, P, B, P, drop_p, seeds[1])
         logits = torch.empty(B, BIMODAL_CLASSES, dtype=torch.float32, device=self.device)
         L.gru_linear_fwd(proj, P, A("classifier.weight"), A("classifier.bias"), logits, BIMODAL_CLASSES, B, BIMODAL_CLASSES, P)
-        return logits, dict(raw=raw, x=x, inv=inv, xm=xm, st=st, comb=comb, h2=h2, proj=proj)
+        return logits, dict(raw=raw, x=x, inv=inv, xm=xm, st=st, comb=comb, h2=h2, proj=proj, drop_p=drop_p, seeds=seeds)
 
     def _gru_param_grads(self, name, s, x, ldx, dx, lddx, B, n_in, hid):
         """the products over all T behind the backward chain: dW_ih, db_ih, dx from dgi; dW_hh, db_hh from dgh and h_{t-1}"""
@@ -182,63 +187,10 @@ class BimodalEngine(MMRCAEngine):
         L.hier_norm_bwd(dx, sv["raw"], sv["inv"], draw, B, ld, so, 1, 0.0, 0, 0)
         return draw
 
-    # ------------------------------------------------------------------ whole model
-    def forward(self, ids, mask, images, drop_p: float = 0.0, seed: int = 0, save: bool = True, enc_drop_p: float = 0.0,
-                text_pack: Optional[TextPack] = None, bn_train: bool = False):
-        """ids/mask int64 [B,T] and images fp32 [B,3,H,W] in HBM -> logits fp32 [B, 4].  drop_p: dropout1's and dropout2's probability.
-        Row b of the batch is time step b of the three GRUs."""
-        for t, nm in ((ids, "input ids"), (mask, "attention mask"), (images, "images")):
-            if t is None or not t.is_cuda:
-                raise L.MmrcaError(f"{nm} must be in HBM; the bimodal path has no CPU fallback")
-        if not 0.0 <= float(drop_p) < 1.0:
-            raise ValueError(f"drop_p must be in [0, 1), got {drop_p}")
-        self.refresh_working_copy()
-        self._plane_valid.clear()
-        self._plane_fresh.clear()
-        B = ids.shape[0]
-        main = torch.cuda.current_stream()
-        if self._text_stream is not None:
-            self._text_stream.wait_stream(main)
-            with torch.cuda.stream(self._text_stream):
-                cls, tsv = self._text_forward(ids, mask, save, enc_drop_p, int(seed), text_pack)
-            feat, vsv = self._image_forward(images, save, bn_train, int(seed))
-            main.wait_stream(self._text_stream)
-            cls.record_stream(main)
-        else:
-            cls, tsv = self._text_forward(ids, mask, save, enc_drop_p, int(seed), text_pack)
-            feat, vsv = self._image_forward(images, save, bn_train, int(seed))
-        # the same seed stride per step as the encoders' site seeds: replay r of a captured step draws eager step seed + r's masks
-        seeds = (self._site_seed(int(seed), 255, 0), self._site_seed(int(seed), 255, 1))
-        logits, hsv = self._head_forward(cls, feat, B, float(drop_p), seeds)
-        hsv.update(drop_p=float(drop_p), seeds=seeds)
-        self._saved = dict(B=B, head=hsv, text=tsv, vision=vsv, full=save)
-        return logits
-
-    def backward(self, dlogits, train_text: bool = True, train_image: bool = True):
-        """accumulates into the gradient arena: the head always, each backbone when its flag is set"""
-        sv = self._saved
-        if sv is None:
-            raise L.MmrcaError("backward() without a forward()")
-        if (train_text or train_image) and not sv["full"]:
-            raise L.MmrcaError("backward through the encoders needs forward(save=True)")
+    def _head_grads(self, dl, sv, train_text, train_image):
         B = sv["B"]
-        dl = dlogits.to(torch.float32).contiguous()
         draw = self._head_backward(dl, sv["head"], B, train_text or train_image)
         self._ready("head", flush=not (train_image or train_text))
         dimg = draw[:B, self.d_txt:].to(self.dtype).contiguous() if train_image else None
         dtxt = draw[:B, :self.d_txt].to(self.dtype).contiguous() if train_text else None
-        main = torch.cuda.current_stream()
-        if train_text and self._text_stream is not None:
-            self._text_stream.wait_stream(main)
-            dtxt.record_stream(self._text_stream)
-            if train_image:
-                self._image_backward(dimg, sv["vision"])
-            with torch.cuda.stream(self._text_stream):
-                self._text_backward(dtxt, sv["text"])
-            main.wait_stream(self._text_stream)
-        else:
-            if train_image:
-                self._image_backward(dimg, sv["vision"])
-            if train_text:
-                self._text_backward(dtxt, sv["text"])
-        self.arena.lp_valid = False
+        return dtxt, dimg

@@ -13,10 +13,17 @@ Data layout in HBM (sized for 288 GB: nothing is recomputed, every saved activat
   arena, which is exactly the reference's gradient-accumulation semantic (main_both.py:112-124).
 
 PyTorch is used for memory, streams and a few index copies only; every arithmetic op is a libmmrca call.
+
+``MMRCAEngine`` is also the base class of the other engines (bimodal_engine, hierarchical_engine, classifier_engine and, through
+the latter, mobilebert_engine): ``parse_dtype`` + ``MMRCAEngine._build`` are the one constructor core, the step helpers
+(``_check_resident``, ``_begin_step``, ``_begin_backward``, ``_encoders_forward``, ``_encoders_backward``) the one step preamble, and
+``_text_entries`` / ``_head_entries`` / ``_head_forward`` / ``_head_grads`` the hooks a subclass fills in.
 """
 from __future__ import annotations
 
 import math
+import os
+import re
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -24,8 +31,6 @@ import torch
 from . import lib as L
 from . import spec as S
 from .conv_engine import ConvEncoder, CONV_MODELS
-
-import os
 
 ALIGN = 64          # arena entries start on 256-byte boundaries
 # text encoder and vision encoder are independent until the fusion head: run them on two streams
@@ -135,8 +140,29 @@ def make_text_pack(attention_mask, device) -> Optional["TextPack"]:
     return TextPack(to(perm, torch.int64), to(cu, torch.int32), to(m.reshape(-1)[perm], torch.int32), to(cu[:-1], torch.int64), M, B, T)
 
 
+def parse_dtype(dtype) -> Tuple[torch.dtype, bool, bool]:
+    """(storage / compute dtype, x3, x3f) of a ``dtype`` argument: "bf16" | "fp32" | "f32" | "bf16x3" | "x3" | "bf16x3f" | "x3f" or a
+    torch dtype (the split-bf16 modes store fp32)"""
+    name = dtype.lower() if isinstance(dtype, str) else ""
+    x3 = name in ("bf16x3", "x3", "bf16x3f", "x3f")
+    if x3:
+        dtype = torch.float32
+    elif isinstance(dtype, str):
+        dtype = {"bf16": torch.bfloat16, "fp32": torch.float32, "f32": torch.float32}[name]
+    return dtype, x3, name in ("bf16x3f", "x3f")
+
+
 class MMRCAEngine:
-    """Owns parameters, gradients and activations of one MM-RCA replica on one GPU."""
+    """Owns parameters, gradients and activations of one MM-RCA replica on one GPU.
+
+    Also the base of the engine family ("The engine family"): ``_build`` is the one place that makes the arena, the
+    parameter groups and the buffer state, ``_check_resident`` / ``_begin_step`` / ``_begin_backward`` / ``_encoders_forward`` /
+    ``_encoders_backward`` are the step's shared pieces, and a subclass says what is its own through ``_text_entries``,
+    ``_head_entries``, ``_head_forward``, ``_head_grads`` and the three class attributes below."""
+
+    OVERLAP_ENCODERS = True         # text and image encoder on two streams (on a GPU, with CONCURRENT_ENCODERS)
+    PATH_NAME = "MM-RCA product"    # "... must be in HBM; the <PATH_NAME> path has no CPU fallback"
+    ENCODER_WORD = "encoders"       # "backward through the <ENCODER_WORD> needs forward(save=True)"
 
     def __init__(self, text_model: str, image_model: str, n_classes: int = 4, reverse: bool = True, mode: int = 0,
                  dtype=torch.bfloat16, device="cuda", gemm_impl: int = L.IMPL_AUTO,
@@ -149,13 +175,7 @@ class MMRCAEngine:
         backward on the hi planes of the saved fp32 activations, bf16 gradient buffers, fp32 gradient accumulation: the fastest
         mode whose logits meet the north-star bound; its gradients are the bf16 mode's, evaluated at fp32-accurate activations."""
         L.load()
-        name = dtype.lower() if isinstance(dtype, str) else ""
-        self.x3 = name in ("bf16x3", "x3", "bf16x3f", "x3f")
-        self.x3f = name in ("bf16x3f", "x3f")
-        if self.x3:
-            dtype = torch.float32
-        elif isinstance(dtype, str):
-            dtype = {"bf16": torch.bfloat16, "fp32": torch.float32, "f32": torch.float32}[dtype.lower()]
+        mode_flags = parse_dtype(dtype)
         if text_model == "bart":
             # the reference accepts the name (multimodal_model.py:137-144, 182-183) but its head is built for 768-wide text
             # features (input_size_txt = 768, :257) while facebook/bart-large emits 1024: its forward fails on the first batch
@@ -165,37 +185,53 @@ class MMRCAEngine:
             raise ValueError(f"Wrong text model: {text_model}")
         if image_model not in S.VISION_SPECS and image_model not in CONV_MODELS:
             raise ValueError(f"Wrong image model: {image_model}")
-        self.ts = S.TEXT_SPECS[text_model]
-        self.vs = S.VISION_SPECS.get(image_model)
-        self.n_classes, self.reverse, self.mode = n_classes, bool(reverse), int(mode)
-        self.dtype, self.device = dtype, torch.device(device)
-        self.dt = L.dtype_code(dtype)
+        self.reverse, self.mode = bool(reverse), int(mode)
+        self._build(mode_flags, device, n_classes, gemm_impl, attn_impl, S.TEXT_SPECS[text_model], image_model, image_size)
+        self._head_w = self._head_struct("p")
+        self._head_g = self._head_struct("g")
+
+    def _build(self, mode_flags, device, n_classes, gemm_impl, attn_impl, text_spec=None, image_model=None, image_size: int = 224):
+        """The core of every engine: compute-mode flags, the backbones (`text_spec` / `image_model`, None = no such backbone; an
+        image model without a ViT spec is a conv backbone), the arena  text | image | head  with its spans and groups, and the
+        buffer state.  mode_flags = ``parse_dtype(dtype)``."""
+        self.dtype, self.x3, self.x3f = mode_flags
+        self.device, self.n_classes = torch.device(device), n_classes
+        self.dt = L.dtype_code(self.dtype)
         # dtype of the gradient buffers / of every backward kernel (bf16x3f: a bf16 backward behind an fp32-accurate forward)
-        self.gdtype = torch.bfloat16 if self.x3f else dtype
+        self.gdtype = torch.bfloat16 if self.x3f else self.dtype
         self.bdt = L.BF16 if self.x3f else self.dt
         self.gemm_impl, self.attn_impl = gemm_impl, attn_impl
+        self.ts = text_spec
+        self.vs = S.VISION_SPECS.get(image_model)
+        is_conv = image_model is not None and self.vs is None
         # bf16x3f with a conv image backbone: the conv kernels run in bf16 (on the hi planes of the weights) next to the fp32-accurate text
         # encoder.  Measured on the initialisation the model trains from (tools/conv_feature_error.py, 480 x 480): of the bf16 mode's
         # logits error (1.0e-3 EfficientNetV2-M, 1.5e-3 -L) the TEXT encoder's bf16 feature carries 7.8e-4 / 1.3e-3 and the conv backbone's
         # 3.9e-4 / 5.4e-4 -- BatchNorm renormalises every layer -- so this split meets the 1e-3 bound at nearly the bf16 mode's speed,
         # where the all-fp32 conv kernels of bf16x3 run at a fifth of it.
-        self.conv_dtype = torch.bfloat16 if (self.x3f and image_model in CONV_MODELS) else None
-        # conv image backbones (EfficientNetV2-M/L, ShuffleNetV2): conv_engine.ConvEncoder over csrc/conv.hip
-        self.conv = ConvEncoder(image_model, self, image_size) if self.vs is None else None
-        self.d_txt, self.d_img = self.ts.dim, (self.vs.dim if self.vs is not None else self.conv.dim)
-        ents = [("text_model." + k, s) for k, s in S.text_params(self.ts)]
-        vis_ents = S.vision_params(self.vs) if self.vs is not None else self.conv.param_entries()
-        ents += [("image_model." + k, s) for k, s in vis_ents]
+        self.conv_dtype = torch.bfloat16 if (self.x3f and is_conv) else None
+        # conv image backbones (EfficientNetV2-M/L, ShuffleNetV2, MobileNetV3): conv_engine.ConvEncoder over csrc/conv.hip
+        self.conv = ConvEncoder(image_model, self, image_size) if is_conv else None
+        self.d_txt = self.ts.dim if self.ts is not None else 0
+        self.d_img = self.vs.dim if self.vs is not None else (self.conv.dim if is_conv else 0)
+        text = [("text_model." + k, s) for k, s in self._text_entries()] if self.ts is not None else []
+        image = []
+        if image_model is not None:
+            image = [("image_model." + k, s) for k, s in (S.vision_params(self.vs) if self.vs is not None else self.conv.param_entries())]
         self.head_keys = self._head_entries()
-        ents += self.head_keys
-        self.arena = Arena(ents, self.device, with_lp=(dtype == torch.bfloat16 or self.x3), with_lo=self.x3)
+        ents = text + image + self.head_keys
+        self.arena = Arena(ents, self.device, with_lp=(self.dtype == torch.bfloat16 or self.x3), with_lo=self.x3)
         self.param_keys = [k for k, _ in ents]
-        self.text_span = self.arena.span(ents[0][0], "text_model." + S.text_params(self.ts)[-1][0])
-        self.image_span = self.arena.span("image_model." + vis_ents[0][0], "image_model." + vis_ents[-1][0])
+        if text and image:
+            self.text_span = self.arena.span(text[0][0], text[-1][0])
+            self.image_span = self.arena.span(image[0][0], image[-1][0])
+        else:
+            self.encoder_span = self.arena.span((text or image)[0][0], (text or image)[-1][0])
         if self.conv is not None:
             self.conv.init_buffers(self.device)
         self.head_span = self.arena.span(self.head_keys[0][0], self.head_keys[-1][0])
         self._bufs: Dict[Tuple, torch.Tensor] = {}
+        self.buffer_generation = 0     # release_buffers() count: captured HIP graphs point into the buffers (GraphedTrainStep checks)
         # bf16x3: gelu(h) and its gradient only feed other bf16x3 GEMMs, so their epilogues write them as two bf16 planes
         self._g_planes = self.x3
         self._plane_valid = set()
@@ -217,24 +253,21 @@ class MMRCAEngine:
             hi = starts[j + 1][1] if j + 1 < len(starts) else self.arena.total
             self.groups[gname] = (lo, hi)
         self.grad_sync = None          # distributed.GradSync, set by the training driver
-        on_gpu = self.device.type == "cuda"
         # (weight gradients run on the stream of their encoder's backward: a second stream for them measured -4 %.  bench.py's
         # single-stream replay still saves and clears these three attributes.)
         self._side_v = self._side_t = self._side = None
-        self._text_stream = torch.cuda.Stream(device=self.device) if (CONCURRENT_ENCODERS and on_gpu) else None
-        self._head_w = self._head_struct("p")
-        self._head_g = self._head_struct("g")
-        # fused QKV views of the text encoder must be contiguous in the arena
-        for i in range(self.ts.layers):
-            K = S.text_layer_keys(self.ts, i)
-            o = [self.arena.offsets["text_model." + K[n] + ".weight"] for n in ("q", "k", "v")]
-            assert o[1][0] == o[0][0] + o[0][2] and o[2][0] == o[1][0] + o[1][2], "qkv weights not adjacent"
-            o = [self.arena.offsets["text_model." + K[n] + ".bias"] for n in ("q", "k", "v")]
-            assert o[1][0] == o[0][0] + o[0][2] and o[2][0] == o[1][0] + o[1][2], "qkv biases not adjacent"
+        overlap = self.OVERLAP_ENCODERS and CONCURRENT_ENCODERS and self.device.type == "cuda"
+        self._text_stream = torch.cuda.Stream(device=self.device) if overlap else None
+        if self.ts in S.TEXT_SPECS.values():
+            # fused QKV views of the text encoder must be contiguous in the arena
+            for i in range(self.ts.layers):
+                K = S.text_layer_keys(self.ts, i)
+                for leaf in (".weight", ".bias"):
+                    o = [self.arena.offsets["text_model." + K[n] + leaf] for n in ("q", "k", "v")]
+                    assert o[1][0] == o[0][0] + o[0][2] and o[2][0] == o[1][0] + o[1][2], f"qkv {leaf[1:]} not adjacent"
 
     @staticmethod
     def _group_of(key: str) -> str:
-        import re
         m = re.match(r"text_model\.(?:transformer|encoder)\.layer\.(\d+)\.", key)
         if m:
             return f"text_layer_{int(m.group(1))}"
@@ -267,9 +300,13 @@ class MMRCAEngine:
             self.grad_sync.span_ready(lo, hi, flush)
 
     # ------------------------------------------------------------------ parameters
+    def _text_entries(self):
+        """(key, shape) of the text encoder's parameters, in arena order, without the "text_model." prefix"""
+        return S.text_params(self.ts)
+
     def _head_entries(self):
-        """(key, shape) of the head's parameters, in arena order (a subclass with another head over the same encoders overrides this and
-        ``_head_struct``)"""
+        """(key, shape) of the head's parameters, in arena order (a subclass with another head overrides this; ``_build`` calls it once
+        ``d_txt`` / ``d_img`` are known)"""
         return S.head_used_params(self.d_img, self.d_txt, self.n_classes, self.mode == 1, self.mode == 2)
 
     def _head_struct(self, which) -> L.HeadPtrs:
@@ -444,7 +481,7 @@ class MMRCAEngine:
         return t
 
     def release_buffers(self):
-        self.buffer_generation = getattr(self, "buffer_generation", 0) + 1     # captured HIP graphs point into these buffers (GraphedTrainStep checks)
+        self.buffer_generation += 1
         self._bufs.clear()
         self._plane_valid.clear()
         self._plane_fresh.clear()
@@ -674,15 +711,45 @@ class MMRCAEngine:
         return cls, dict(B=B, T=T, M=M, cu=cu, first=first, ids32=ids32, pos=pos, mask32=mask32, emb=emb, mean0=mean0, rstd0=rstd0, layers=layers,
                          drop_p=dp, drop_seed=drop_seed, taps=tap_rows)
 
+    def _text_upper_backward(self, dy, sv, i, K, rows, cap, sfx):
+        """The half of text layer i's backward above the attention: LN2 -> FFN2 -> FFN1 -> LN1 -> out-projection on `rows` rows, with
+        gradient buffers ``tg_<name><sfx>`` of `cap` rows (all rows: M, B*T, ""; class-token tail: B, B, "_c", against the saved
+        ``ctx_c``).  dy: gradient at the layer output, K: the layer's keys.  Returns (ds1, dctx): the gradient of the residual
+        stream below LN1 and of the attention context."""
+        s, P = self.ts, "text_model."
+        D, Fd = s.dim, s.ffn
+        a = sv["layers"][i]
+        gb = lambda name, cols: self.buf("tg_" + name + sfx, cap, cols, self.gdtype)
+        dp, sd = sv["drop_p"], (lambda layer, site: self._site_seed(sv["drop_seed"], layer, site))
+        post_attn_drop = dp if s.name != "distilbert" else 0.0
+        ds2 = gb("ds2", D)
+        df = gb("dbr_ffn", D) if dp > 0 else None      # gradient of the dropped FFN branch
+        gb_f2, gb_o = self.G(P + K["f2"] + ".bias"), self.G(P + K["o"] + ".bias")
+        # the LayerNorm backward also emits the column sums of its output = bias gradient of the linear that fed it
+        self._ln_bwd(dy, a["s2"], P + K["ln2"], a["m2"], a["r2"], None, ds2, rows, D, branch_drop=(dp, sd(i, 3)), dbranch=df,
+                     dcol=(None if df is not None else gb_f2), dcol_branch=(gb_f2 if df is not None else None))
+        dg = self.planes_buf("tg_dF" + sfx, cap, Fd) if (self._g_planes and not self.x3f) else gb("dF", Fd)
+        self._lin_bwd(df if df is not None else ds2, a["g"], P + K["f2"] + ".weight", P + K["f2"] + ".bias", dg, rows, D, Fd,
+                      gelu_h=a["h"], bias_done=True, gelu_db=self.G(P + K["f1"] + ".bias"))
+        dx1 = gb("dxB", D)
+        self._lin_bwd(dg, a["x1"], P + K["f1"] + ".weight", P + K["f1"] + ".bias", dx1, rows, Fd, D, addend=ds2, bias_done=True)
+        ds1 = gb("ds1", D)
+        datt = gb("dbr_att", D) if post_attn_drop > 0 else None
+        self._ln_bwd(dx1, a["s1"], P + K["ln1"], a["m1"], a["r1"], None, ds1, rows, D, branch_drop=(post_attn_drop, sd(i, 2)), dbranch=datt,
+                     dcol=(None if datt is not None else gb_o), dcol_branch=(gb_o if datt is not None else None))
+        dctx = gb("dctx", D)
+        self._lin_bwd(datt if datt is not None else ds1, a["ctx_c" if sfx else "ctx"], P + K["o"] + ".weight", P + K["o"] + ".bias", dctx,
+                      rows, D, D, bias_done=True)
+        return ds1, dctx
+
     def _text_backward(self, dcls, sv, dtaps=None):
         """dtaps (optional): {hidden_states index n: gradient [B, D] at its class-token rows}, added into the residual-stream gradient
         at the output of layer n - 1 before that layer's backward runs"""
         s, P = self.ts, "text_model."
         B, T = sv["B"], sv["T"]
-        M, D, Fd, H = sv["M"], s.dim, s.ffn, s.heads
+        M, D, H = sv["M"], s.dim, s.heads
         dh, cu, first = D // H, sv["cu"], sv["first"]
         gb = lambda name, cols: self.buf("tg_" + name, B * T, cols, self.gdtype)
-        gplanes = self._g_planes and not self.x3f
         dx = gb("dxA", D)
         tail = bool(sv["layers"][-1].get("tail"))
         if not tail:
@@ -695,31 +762,12 @@ class MMRCAEngine:
             K, a = S.text_layer_keys(s, i), sv["layers"][i]
             if dtaps and (i + 1) in dtaps:
                 dx.index_add_(0, first, dtaps[i + 1].to(dx.dtype))
-            ds2 = gb("ds2", D)
-            dp, sd = sv["drop_p"], (lambda layer, site: self._site_seed(sv["drop_seed"], layer, site))
-            post_attn_drop = dp if s.name != "distilbert" else 0.0
-            df = gb("dbr_ffn", D) if dp > 0 else None      # gradient of the dropped FFN branch
-            gb_f2, gb_o = self.G(P + K["f2"] + ".bias"), self.G(P + K["o"] + ".bias")
-            # the LayerNorm backward also emits the column sums of its output = bias gradient of the linear that fed it
-            self._ln_bwd(dx, a["s2"], P + K["ln2"], a["m2"], a["r2"], None, ds2, M, D, branch_drop=(dp, sd(i, 3)), dbranch=df,
-                         dcol=(None if df is not None else gb_f2), dcol_branch=(gb_f2 if df is not None else None))
-            dg = self.planes_buf("tg_dF", B * T, Fd) if gplanes else gb("dF", Fd)
-            self._lin_bwd(df if df is not None else ds2, a["g"], P + K["f2"] + ".weight", P + K["f2"] + ".bias", dg, M, D, Fd,
-                          gelu_h=a["h"], bias_done=True, gelu_db=self.G(P + K["f1"] + ".bias"))
-            dx1 = gb("dxB", D)
-            self._lin_bwd(dg, a["x1"], P + K["f1"] + ".weight", P + K["f1"] + ".bias", dx1, M, Fd, D, addend=ds2, bias_done=True)
-            ds1 = gb("ds1", D)
-            datt = gb("dbr_att", D) if post_attn_drop > 0 else None
-            self._ln_bwd(dx1, a["s1"], P + K["ln1"], a["m1"], a["r1"], None, ds1, M, D, branch_drop=(post_attn_drop, sd(i, 2)), dbranch=datt,
-                         dcol=(None if datt is not None else gb_o), dcol_branch=(gb_o if datt is not None else None))
-            dctx = gb("dctx", D)
-            self._lin_bwd(datt if datt is not None else ds1, a["ctx"], P + K["o"] + ".weight", P + K["o"] + ".bias", dctx, M, D, D,
-                          bias_done=True)
+            ds1, dctx = self._text_upper_backward(dx, sv, i, K, M, B * T, "")
             dqkv = gb("dqkv", 3 * D)
             # the attention backward also reduces the q|k|v bias gradients (adjacent in the arena) while it has the tiles
             qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "tg", B * T, B)
             L.mha_bwd(qkv_b, sv["mask32"], ctx_b, dctx, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt, self.attn_impl,
-                      drop_p=dp, drop_seed=sd(i, 1), cu=cu)
+                      drop_p=sv["drop_p"], drop_seed=self._site_seed(sv["drop_seed"], i, 1), cu=cu)
             self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1, wnumel=3 * D * D)
             self._ready(f"text_layer_{i}")
         ds0 = gb("ds2", D)
@@ -735,32 +783,13 @@ class MMRCAEngine:
         """Backward of the LAST text layer when its post-attention part ran on the class-token rows only (CLS_TAIL)."""
         s, P = self.ts, "text_model."
         B, T = sv["B"], sv["T"]
-        M, D, Fd, H = sv["M"], s.dim, s.ffn, s.heads
+        M, D, H = sv["M"], s.dim, s.heads
         dh, i, cu, first = D // H, s.layers - 1, sv["cu"], sv["first"]
         K, a = S.text_layer_keys(s, i), sv["layers"][i]
         gb = lambda name, cols: self.buf("tg_" + name, B * T, cols, self.gdtype)
-        gc = lambda name, cols: self.buf("tg_" + name + "_c", B, cols, self.gdtype)
-        dp, sd = sv["drop_p"], (lambda layer, site: self._site_seed(sv["drop_seed"], layer, site))
-        post_attn_drop = dp if s.name != "distilbert" else 0.0
-        dxc = gc("dx", D)
+        dxc = self.buf("tg_dx_c", B, D, self.gdtype)
         dxc[:B].copy_(dcls)
-        ds2 = gc("ds2", D)
-        df = gc("dbr_ffn", D) if dp > 0 else None
-        gb_f2, gb_o = self.G(P + K["f2"] + ".bias"), self.G(P + K["o"] + ".bias")
-        self._ln_bwd(dxc, a["s2"], P + K["ln2"], a["m2"], a["r2"], None, ds2, B, D, branch_drop=(dp, sd(i, 3)), dbranch=df,
-                     dcol=(None if df is not None else gb_f2), dcol_branch=(gb_f2 if df is not None else None))
-        dg = self.planes_buf("tg_dF_c", B, Fd) if (self._g_planes and not self.x3f) else gc("dF", Fd)
-        self._lin_bwd(df if df is not None else ds2, a["g"], P + K["f2"] + ".weight", P + K["f2"] + ".bias", dg, B, D, Fd,
-                      gelu_h=a["h"], bias_done=True, gelu_db=self.G(P + K["f1"] + ".bias"))
-        dx1 = gc("dxB", D)
-        self._lin_bwd(dg, a["x1"], P + K["f1"] + ".weight", P + K["f1"] + ".bias", dx1, B, Fd, D, addend=ds2, bias_done=True)
-        ds1 = gc("ds1", D)
-        datt = gc("dbr_att", D) if post_attn_drop > 0 else None
-        self._ln_bwd(dx1, a["s1"], P + K["ln1"], a["m1"], a["r1"], None, ds1, B, D, branch_drop=(post_attn_drop, sd(i, 2)), dbranch=datt,
-                     dcol=(None if datt is not None else gb_o), dcol_branch=(gb_o if datt is not None else None))
-        dctx_c = gc("dctx", D)
-        self._lin_bwd(datt if datt is not None else ds1, a["ctx_c"], P + K["o"] + ".weight", P + K["o"] + ".bias", dctx_c, B, D, D,
-                      bias_done=True)
+        ds1, dctx_c = self._text_upper_backward(dxc, sv, i, K, B, B, "_c")
         # back to all rows: the attention mixes the class-token gradient into every key / value row
         ds1_full = gb("ds1", D)
         ds1_full[:M].zero_()
@@ -768,7 +797,7 @@ class MMRCAEngine:
         dqkv = gb("dqkv", 3 * D)
         qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "tg", B * T, B)
         L.mha_cls_bwd(qkv_b, sv["mask32"], ctx_b, dctx_c, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt,
-                      drop_p=dp, drop_seed=sd(i, 1), cu=cu)
+                      drop_p=sv["drop_p"], drop_seed=self._site_seed(sv["drop_seed"], i, 1), cu=cu)
         self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1_full, wnumel=3 * D * D)
         self._ready(f"text_layer_{i}")
 
@@ -860,13 +889,32 @@ class MMRCAEngine:
             self._ln_fwd(pend[0], pend[1], P + "encoder.ln", x, feat, mf, rf, B, D, s.ln_eps, ld_x=Tn * D, ld_y=D)
         return feat[:B], dict(B=B, patches=patches, xL=x, mf=mf, rf=rf, layers=layers)
 
+    def _vision_upper_backward(self, dx, sv, i, rows, sfx):
+        """The half of ViT layer i's backward above the attention: FFN2 -> FFN1 -> LN2 -> out-projection on `rows` rows (all rows:
+        B*Tn, buffers ``vg_<name>``; class-token tail: B, ``vg_<name>_c``).  dx: gradient at the layer output.  Returns (dctx, dx1):
+        the gradient of the attention context and of the residual stream below LN2."""
+        s = self.vs
+        D, Fd = s.dim, s.ffn
+        Lk, a = f"image_model.encoder.layers.encoder_layer_{i}.", sv["layers"][i]
+        gb = lambda name, cols: self.buf("vg_" + name + sfx, rows, cols, self.gdtype)
+        dg = self.planes_buf("vg_dF" + sfx, rows, Fd) if (self._g_planes and not self.x3f) else gb("dF", Fd)
+        self._lin_bwd(dx, a["g"], Lk + "mlp.3.weight", Lk + "mlp.3.bias", dg, rows, D, Fd, gelu_h=a["h"], bias_done=True,
+                      gelu_db=self.G(Lk + "mlp.0.bias"))
+        dy2 = gb("dy", D)
+        self._lin_bwd(dg, a["y2"], Lk + "mlp.0.weight", Lk + "mlp.0.bias", dy2, rows, Fd, D, bias_done=True)
+        dx1 = gb("dxB", D)
+        self._ln_bwd(dy2, a["x1"], Lk + "ln_2", a["m2"], a["r2"], dx, dx1, rows, D, dcol=self.G(Lk + "self_attention.out_proj.bias"))
+        dctx = gb("dctx", D)
+        self._lin_bwd(dx1, a["ctx_c" if sfx else "ctx"], Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", dctx,
+                      rows, D, D, bias_done=True)
+        return dctx, dx1
+
     def _vision_backward(self, dfeat, sv):
         s, P = self.vs, "image_model."
         B = sv["B"]
-        nP, Tn, D, Fd, H = s.tokens - 1, s.tokens, s.dim, s.ffn, s.heads
+        nP, Tn, D, H = s.tokens - 1, s.tokens, s.dim, s.heads
         dh, M, Kp = D // H, B * Tn, 3 * s.patch * s.patch
         gb = lambda name, rows, cols: self.buf("vg_" + name, rows, cols, self.gdtype)
-        gplanes = self._g_planes and not self.x3f
         dx = gb("dxA", M, D)
         dfe = gb("dfeat", B, D)
         dfe[:B].copy_(dfeat)
@@ -886,16 +934,7 @@ class MMRCAEngine:
                 self._vision_backward_tail(dxc, sv, dx)
                 continue
             Lk, a = P + f"encoder.layers.encoder_layer_{i}.", sv["layers"][i]
-            dg = self.planes_buf("vg_dF", M, Fd) if gplanes else gb("dF", M, Fd)
-            self._lin_bwd(dx, a["g"], Lk + "mlp.3.weight", Lk + "mlp.3.bias", dg, M, D, Fd, gelu_h=a["h"], bias_done=True,
-                          gelu_db=self.G(Lk + "mlp.0.bias"))
-            dy2 = gb("dy", M, D)
-            self._lin_bwd(dg, a["y2"], Lk + "mlp.0.weight", Lk + "mlp.0.bias", dy2, M, Fd, D, bias_done=True)
-            dx1 = gb("dxB", M, D)
-            self._ln_bwd(dy2, a["x1"], Lk + "ln_2", a["m2"], a["r2"], dx, dx1, M, D, dcol=self.G(Lk + "self_attention.out_proj.bias"))
-            dctx = gb("dctx", M, D)
-            self._lin_bwd(dx1, a["ctx"], Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", dctx, M, D, D,
-                          bias_done=True)
+            dctx, dx1 = self._vision_upper_backward(dx, sv, i, M, "")
             dqkv = gb("dqkv", M, 3 * D)
             qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "vg", M, B)
             L.mha_bwd(qkv_b, None, ctx_b, dctx, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt, self.attn_impl)
@@ -914,21 +953,11 @@ class MMRCAEngine:
         dxc [B, D] is the gradient at the layer's class-token output, dx [B*Tn, D] receives the gradient at its input."""
         s, P = self.vs, "image_model."
         B = sv["B"]
-        Tn, D, Fd, H = s.tokens, s.dim, s.ffn, s.heads
+        Tn, D, H = s.tokens, s.dim, s.heads
         dh, M, i = D // H, B * Tn, s.layers - 1
         Lk, a = P + f"encoder.layers.encoder_layer_{i}.", sv["layers"][i]
         gb = lambda name, rows, cols: self.buf("vg_" + name, rows, cols, self.gdtype)
-        gc = lambda name, cols: self.buf("vg_" + name + "_c", B, cols, self.gdtype)
-        dg = self.planes_buf("vg_dF_c", B, Fd) if (self._g_planes and not self.x3f) else gc("dF", Fd)
-        self._lin_bwd(dxc, a["g"], Lk + "mlp.3.weight", Lk + "mlp.3.bias", dg, B, D, Fd, gelu_h=a["h"], bias_done=True,
-                      gelu_db=self.G(Lk + "mlp.0.bias"))
-        dy2 = gc("dy", D)
-        self._lin_bwd(dg, a["y2"], Lk + "mlp.0.weight", Lk + "mlp.0.bias", dy2, B, Fd, D, bias_done=True)
-        dx1c = gc("dxB", D)
-        self._ln_bwd(dy2, a["x1"], Lk + "ln_2", a["m2"], a["r2"], dxc, dx1c, B, D, dcol=self.G(Lk + "self_attention.out_proj.bias"))
-        dctx_c = gc("dctx", D)
-        self._lin_bwd(dx1c, a["ctx_c"], Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", dctx_c, B, D, D,
-                      bias_done=True)
+        dctx_c, dx1c = self._vision_upper_backward(dxc, sv, i, B, "_c")
         # back to all rows: the attention mixes the class-token gradient into every key / value row, and the residual
         # stream carries it straight down at the class-token rows
         dx1 = gb("dxB", M, D)
@@ -943,43 +972,32 @@ class MMRCAEngine:
         self._ln_bwd(dy1, a["x"], Lk + "ln_1", a["m1"], a["r1"], dx1, dx, M, D, dcol=(self.G(below) if i > 0 else None))
         self._ready(f"image_layer_{i}")
 
-    # ------------------------------------------------------------------ whole model
+    # ------------------------------------------------------------------ whole model: the step's shared pieces
+    def _check_resident(self, *named):
+        """(tensor, name) pairs an engine is about to read: each must be in HBM"""
+        for t, nm in named:
+            if t is None or not t.is_cuda:
+                raise L.MmrcaError(f"{nm} must be in HBM; the {self.PATH_NAME} path has no CPU fallback")
+
+    def _begin_step(self):
+        self.refresh_working_copy()
+        self._plane_valid.clear()
+        self._plane_fresh.clear()
+
+    def _begin_backward(self, dlogits, train_enc):
+        """-> (what forward() saved, dlogits as contiguous fp32)"""
+        sv = self._saved
+        if sv is None:
+            raise L.MmrcaError("backward() without a forward()")
+        if train_enc and not sv["full"]:
+            raise L.MmrcaError(f"backward through the {self.ENCODER_WORD} needs forward(save=True)")
+        return sv, dlogits.to(torch.float32).contiguous()
+
     def _image_forward(self, images, save, bn_train, seed):
         if self.conv is not None:
             feat = self.conv.forward(images, save, bn_train, seed)
             return (feat.to(self.dtype) if feat.dtype != self.dtype else feat), None       # (bf16 conv features under an fp32 head)
         return self._vision_forward(images, save)
-
-    def forward(self, ids, mask, images, drop_p: float = 0.0, seed: int = 0, save: bool = True, enc_drop_p: float = 0.0,
-                text_pack: Optional[TextPack] = None, bn_train: bool = False):
-        """ids/mask int64 [B,S] and images fp32 [B,3,H,W] in HBM -> logits fp32 [B, n_classes].
-        text_pack (``make_text_pack`` of the same batch's host-side mask): run the text encoder on the live tokens only."""
-        for t, nm in ((ids, "input ids"), (mask, "attention mask"), (images, "images")):
-            if not t.is_cuda:
-                raise L.MmrcaError(f"{nm} must be in HBM; the MM-RCA product path has no CPU fallback")
-        self.refresh_working_copy()
-        self._plane_valid.clear()
-        self._plane_fresh.clear()
-        B = ids.shape[0]
-        main = torch.cuda.current_stream()
-        if self._text_stream is not None:
-            self._text_stream.wait_stream(main)
-            with torch.cuda.stream(self._text_stream):
-                cls, tsv = self._text_forward(ids, mask, save, enc_drop_p, int(seed), text_pack)
-            feat, vsv = self._image_forward(images, save, bn_train, int(seed))
-            main.wait_stream(self._text_stream)
-            cls.record_stream(main)
-        else:
-            cls, tsv = self._text_forward(ids, mask, save, enc_drop_p, int(seed), text_pack)
-            feat, vsv = self._image_forward(images, save, bn_train, int(seed))
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        # the head's mask seed advances by the same stride per step as the encoders' site seeds: a HIP-graph replay r of this step then
-        # draws the masks of step seed + r everywhere (lib.seed_epoch_set)
-        head_seed = self._site_seed(int(seed), 255, 0)
-        L.head_fwd(feat, cls, self._head_w, logits, B, self.d_img, self.d_txt, self.n_classes, self.reverse, self.mode,
-                   float(drop_p), head_seed, self.dt)
-        self._saved = dict(B=B, cls=cls, feat=feat, text=tsv, vision=vsv, drop_p=float(drop_p), seed=head_seed, full=save)
-        return logits
 
     def _image_backward(self, dimg, vsv):
         if self.conv is not None:
@@ -988,35 +1006,79 @@ class MMRCAEngine:
         else:
             self._vision_backward(dimg, vsv)
 
-    def backward(self, dlogits, train_text: bool = True, train_image: bool = True):
-        sv = self._saved
-        if sv is None:
-            raise L.MmrcaError("backward() without a forward()")
-        if (train_text or train_image) and not sv["full"]:
-            raise L.MmrcaError("backward through the encoders needs forward(save=True)")
-        B = sv["B"]
-        dl = dlogits.to(torch.float32).contiguous()
-        dimg = torch.empty(B, self.d_img, dtype=self.dtype, device=self.device) if train_image else None
-        dtxt = torch.empty(B, self.d_txt, dtype=self.dtype, device=self.device) if train_text else None
-        L.head_bwd(dl, sv["feat"], sv["cls"], self._head_w, self._head_g, dimg, dtxt, B, self.d_img, self.d_txt,
-                   self.n_classes, self.reverse, self.mode, sv["drop_p"], sv["seed"], self.dt)
-        self._ready("head", flush=not (train_image or train_text))
+    def _encoders_forward(self, ids, mask, images, save, enc_drop_p, seed, text_pack, bn_train):
+        """both encoders, the text encoder on its own stream when the engine overlaps them -> (cls, text saved, feat, vision saved)"""
+        if self._text_stream is None:
+            cls, tsv = self._text_forward(ids, mask, save, enc_drop_p, seed, text_pack)
+            feat, vsv = self._image_forward(images, save, bn_train, seed)
+            return cls, tsv, feat, vsv
         main = torch.cuda.current_stream()
-        if train_text and self._text_stream is not None:
+        self._text_stream.wait_stream(main)
+        with torch.cuda.stream(self._text_stream):
+            cls, tsv = self._text_forward(ids, mask, save, enc_drop_p, seed, text_pack)
+        feat, vsv = self._image_forward(images, save, bn_train, seed)
+        main.wait_stream(self._text_stream)
+        cls.record_stream(main)
+        return cls, tsv, feat, vsv
+
+    def _encoders_backward(self, dtxt, dimg, sv):
+        """dtxt / dimg: the gradient at the text / image feature, None while that encoder is frozen"""
+        if dtxt is not None and self._text_stream is not None:
             # the host queues the text backward first (it is short) on its own stream, then the vision backward on the
             # main stream; the gradient all-reduce hooks see image groups and text groups on their own streams
+            main = torch.cuda.current_stream()
             self._text_stream.wait_stream(main)
             dtxt.record_stream(self._text_stream)
-            if train_image:
+            if dimg is not None:
                 self._image_backward(dimg, sv["vision"])
             with torch.cuda.stream(self._text_stream):
                 self._text_backward(dtxt, sv["text"])
             main.wait_stream(self._text_stream)
         else:
-            if train_image:
+            if dimg is not None:
                 self._image_backward(dimg, sv["vision"])
-            if train_text:
+            if dtxt is not None:
                 self._text_backward(dtxt, sv["text"])
+
+    # ------------------------------------------------------------------ whole model: the head hooks and the step
+    def _head_forward(self, cls, feat, B, drop_p, seeds):
+        """cls [B, d_txt], feat [B, d_img] -> (logits fp32, what ``_head_grads`` reads back as ``sv["head"]``)"""
+        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
+        L.head_fwd(feat, cls, self._head_w, logits, B, self.d_img, self.d_txt, self.n_classes, self.reverse, self.mode,
+                   drop_p, seeds[0], self.dt)
+        return logits, dict(drop_p=drop_p, seed=seeds[0])
+
+    def _head_grads(self, dl, sv, train_text, train_image):
+        """accumulates the head's parameter gradients, announces the head group and returns (dtxt, dimg): the gradients at the two
+        features in the encoders' dtype, None for a frozen encoder"""
+        B, hsv = sv["B"], sv["head"]
+        dimg = torch.empty(B, self.d_img, dtype=self.dtype, device=self.device) if train_image else None
+        dtxt = torch.empty(B, self.d_txt, dtype=self.dtype, device=self.device) if train_text else None
+        L.head_bwd(dl, sv["feat"], sv["cls"], self._head_w, self._head_g, dimg, dtxt, B, self.d_img, self.d_txt,
+                   self.n_classes, self.reverse, self.mode, hsv["drop_p"], hsv["seed"], self.dt)
+        self._ready("head", flush=not (train_image or train_text))
+        return dtxt, dimg
+
+    def forward(self, ids, mask, images, drop_p: float = 0.0, seed: int = 0, save: bool = True, enc_drop_p: float = 0.0,
+                text_pack: Optional[TextPack] = None, bn_train: bool = False):
+        """ids/mask int64 [B,S] and images fp32 [B,3,H,W] in HBM -> logits fp32 [B, n_classes].
+        text_pack (``make_text_pack`` of the same batch's host-side mask): run the text encoder on the live tokens only."""
+        self._check_resident((ids, "input ids"), (mask, "attention mask"), (images, "images"))
+        self._begin_step()
+        B = ids.shape[0]
+        cls, tsv, feat, vsv = self._encoders_forward(ids, mask, images, save, enc_drop_p, int(seed), text_pack, bn_train)
+        # the head's mask seeds advance by the same stride per step as the encoders' site seeds: a HIP-graph replay r of this step then
+        # draws the masks of step seed + r everywhere (lib.seed_epoch_set)
+        seeds = (self._site_seed(int(seed), 255, 0), self._site_seed(int(seed), 255, 1))
+        logits, hsv = self._head_forward(cls, feat, B, float(drop_p), seeds)
+        self._saved = dict(B=B, cls=cls, feat=feat, text=tsv, vision=vsv, head=hsv, full=save)
+        return logits
+
+    def backward(self, dlogits, train_text: bool = True, train_image: bool = True):
+        """accumulates into the gradient arena: the head always, each encoder when its flag is set"""
+        sv, dl = self._begin_backward(dlogits, train_text or train_image)
+        dtxt, dimg = self._head_grads(dl, sv, train_text, train_image)
+        self._encoders_backward(dtxt, dimg, sv)
         self.arena.lp_valid = False        # an optimizer step normally follows
 
     # ------------------------------------------------------------------ flat-arena optimizer steps

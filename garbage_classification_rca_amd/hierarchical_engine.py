@@ -17,17 +17,20 @@ The head (csrc/hier_head.hip + ``mmrca_linear_cls_*``) is fp32 in every ``dtype`
 Same ``forward`` / ``backward`` / ``trainable_spans`` / ``groups`` contract as the MM-RCA engine, so the flat optimizers, ``GradSync`` and
 ``hip_train_step`` drive it unchanged.  The text encoder and the image encoder run one after the other on the caller's stream: the
 two-stream overlap of the MM-RCA engine is not used here (the taps would need cross-stream hand-overs at two more points per encoder).
+
+The constructor keeps the configuration guard and hands the rest to ``MMRCAEngine._build`` (the segment offsets and the head keys
+come from the ``_head_entries`` hook); ``forward`` / ``backward`` stay this class's own, because the taps land in the head's ``raw``
+buffer between the encoders, and start with the base's ``_check_resident`` / ``_begin_step`` / ``_begin_backward``.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Optional, Tuple
 
 import torch
 
 from . import lib as L
 from . import spec as S
-from .conv_engine import ConvEncoder
-from .engine import Arena, MMRCAEngine, TextPack
+from .engine import MMRCAEngine, TextPack, parse_dtype
 
 HIER_IMAGE_MODELS = ("eff_v2_medium", "EffNetv2-Medium")
 HIER_HIDDEN = 512
@@ -67,6 +70,9 @@ def check_hierarchical_config(text_model: str, image_model: str, image_size: int
 class HierarchicalEngine(MMRCAEngine):
     """Owns parameters, gradients and activations of one hierarchical-fusion replica on one GPU."""
 
+    OVERLAP_ENCODERS = False
+    PATH_NAME = "hierarchical"
+
     def __init__(self, text_model: str, image_model: str = "eff_v2_medium", n_classes: int = 4, dtype="bf16x3f", device="cuda",
                  image_size: int = 480, gemm_impl: int = L.IMPL_AUTO, attn_impl: int = L.IMPL_AUTO):
         """dtype: the four modes of MMRCAEngine (bf16 | fp32 | bf16x3 | bf16x3f; the conv backbone runs bf16 under bf16x3f).  The head
@@ -75,23 +81,10 @@ class HierarchicalEngine(MMRCAEngine):
         if not 1 <= int(n_classes) <= 16:
             raise ValueError(f"n_classes must be in [1, 16], got {n_classes}")
         L.load()
-        name = dtype.lower() if isinstance(dtype, str) else ""
-        self.x3 = name in ("bf16x3", "x3", "bf16x3f", "x3f")
-        self.x3f = name in ("bf16x3f", "x3f")
-        if self.x3:
-            dtype = torch.float32
-        elif isinstance(dtype, str):
-            dtype = {"bf16": torch.bfloat16, "fp32": torch.float32, "f32": torch.float32}[dtype.lower()]
-        self.ts, self.vs = S.TEXT_SPECS[text_model], None
-        self.n_classes, self.reverse, self.mode = int(n_classes), True, 0
-        self.dtype, self.device = dtype, torch.device(device)
-        self.dt = L.dtype_code(dtype)
-        self.gdtype = torch.bfloat16 if self.x3f else dtype
-        self.bdt = L.BF16 if self.x3f else self.dt
-        self.gemm_impl, self.attn_impl = gemm_impl, attn_impl
-        self.conv_dtype = torch.bfloat16 if self.x3f else None
-        self.conv = ConvEncoder(image_model, self, image_size)
-        self.d_txt, self.d_img = self.ts.dim, self.conv.dim
+        self.reverse, self.mode = True, 0
+        self._build(parse_dtype(dtype), device, int(n_classes), gemm_impl, attn_impl, S.TEXT_SPECS[text_model], image_model, image_size)
+
+    def _head_entries(self):
         # columns of raw / x: f | pool(stage3) | pool(stage6) | t0 | t2 | t4
         widths = [self.d_img] + [w for _, _, _, w in HIER_STAGES] + [self.d_txt] * 3
         self.seg_off = [0]
@@ -100,43 +93,9 @@ class HierarchicalEngine(MMRCAEngine):
         self.n_img_segs = 1 + len(HIER_STAGES)
         self.w_img, self.w_all = self.seg_off[self.n_img_segs], self.seg_off[-1]
         self.w_txt = self.w_all - self.w_img
-        ents = [("text_model." + k, s) for k, s in S.text_params(self.ts)]
-        vis_ents = self.conv.param_entries()
-        ents += [("image_model." + k, s) for k, s in vis_ents]
-        self.head_keys = [("final_hierarchical_image.weight", (HIER_HIDDEN, self.w_img)), ("final_hierarchical_image.bias", (HIER_HIDDEN,)),
-                          ("final_hierarchical_text.weight", (HIER_HIDDEN, self.w_txt)), ("final_hierarchical_text.bias", (HIER_HIDDEN,)),
-                          ("final_hierarchical_all.weight", (self.n_classes, 2 * HIER_HIDDEN)), ("final_hierarchical_all.bias", (self.n_classes,))]
-        ents += self.head_keys
-        self.arena = Arena(ents, self.device, with_lp=(dtype == torch.bfloat16 or self.x3), with_lo=self.x3)
-        self.param_keys = [k for k, _ in ents]
-        self.text_span = self.arena.span(ents[0][0], "text_model." + S.text_params(self.ts)[-1][0])
-        self.image_span = self.arena.span("image_model." + vis_ents[0][0], "image_model." + vis_ents[-1][0])
-        self.conv.init_buffers(self.device)
-        self.head_span = self.arena.span(self.head_keys[0][0], self.head_keys[-1][0])
-        self._bufs: Dict[Tuple, torch.Tensor] = {}
-        self._g_planes = self.x3
-        self._plane_valid, self._plane_fresh = set(), set()
-        self._ln_planes = self._g_planes
-        self._gelu_act = L.ACT_GELU_SAVE_GRAD_BF16 if self.x3f else L.ACT_GELU_SAVE_GRAD
-        self._hdt = torch.bfloat16 if self.x3f else None
-        self._saved = None
-        self.groups: Dict[str, Tuple[int, int]] = {}
-        starts = []
-        for k in self.param_keys:
-            gname = self._group_of(k)
-            if not starts or starts[-1][0] != gname:
-                starts.append((gname, self.arena.offsets[k][0]))
-        for j, (gname, lo) in enumerate(starts):
-            hi = starts[j + 1][1] if j + 1 < len(starts) else self.arena.total
-            self.groups[gname] = (lo, hi)
-        self.grad_sync = None
-        self._side_v = self._side_t = self._side = None
-        self._text_stream = None
-        for i in range(self.ts.layers):
-            K = S.text_layer_keys(self.ts, i)
-            for leaf in (".weight", ".bias"):
-                o = [self.arena.offsets["text_model." + K[n] + leaf] for n in ("q", "k", "v")]
-                assert o[1][0] == o[0][0] + o[0][2] and o[2][0] == o[1][0] + o[1][2], "qkv parameters not adjacent"
+        return [("final_hierarchical_image.weight", (HIER_HIDDEN, self.w_img)), ("final_hierarchical_image.bias", (HIER_HIDDEN,)),
+                ("final_hierarchical_text.weight", (HIER_HIDDEN, self.w_txt)), ("final_hierarchical_text.bias", (HIER_HIDDEN,)),
+                ("final_hierarchical_all.weight", (self.n_classes, 2 * HIER_HIDDEN)), ("final_hierarchical_all.bias", (self.n_classes,))]
 
     def _hbuf(self, name, B, cols):
         return self.buf("hier_" + name, B, cols, torch.float32)
@@ -153,14 +112,10 @@ class HierarchicalEngine(MMRCAEngine):
     def forward(self, ids, mask, images, drop_p: float = 0.0, seed: int = 0, save: bool = True, enc_drop_p: float = 0.0,
                 text_pack: Optional[TextPack] = None, bn_train: bool = False):
         """ids/mask int64 [B,T] and images fp32 [B,3,H,W] in HBM -> logits fp32 [B, n_classes].  drop_p: the dropout on xi and on xt."""
-        for t, nm in ((ids, "input ids"), (mask, "attention mask"), (images, "images")):
-            if t is None or not t.is_cuda:
-                raise L.MmrcaError(f"{nm} must be in HBM; the hierarchical path has no CPU fallback")
+        self._check_resident((ids, "input ids"), (mask, "attention mask"), (images, "images"))
         if images.shape[-1] != self.conv.image or images.shape[-2] != self.conv.image:
             raise ValueError(f"images must be [B,3,{self.conv.image},{self.conv.image}], got {tuple(images.shape)}")
-        self.refresh_working_copy()
-        self._plane_valid.clear()
-        self._plane_fresh.clear()
+        self._begin_step()
         B, ld, so = ids.shape[0], self.w_all, self.seg_off
         raw, x, h = self._hbuf("raw", B, ld), self._hbuf("x", B, ld), self._hbuf("h", B, 2 * HIER_HIDDEN)
         inv = self._hbuf("inv", B, len(so) - 1)
@@ -187,14 +142,9 @@ class HierarchicalEngine(MMRCAEngine):
 
     def backward(self, dlogits, train_text: bool = True, train_image: bool = True):
         """accumulates into the gradient arena: the three head linears always, each backbone when its flag is set"""
-        sv = self._saved
-        if sv is None:
-            raise L.MmrcaError("backward() without a forward()")
-        if (train_text or train_image) and not sv["full"]:
-            raise L.MmrcaError("backward through the encoders needs forward(save=True)")
+        sv, dl = self._begin_backward(dlogits, train_text or train_image)
         B, ld, so, x, h = sv["B"], self.w_all, self.seg_off, sv["x"], sv["h"]
         A, H2 = self.arena.view, 2 * HIER_HIDDEN
-        dl = dlogits.to(torch.float32).contiguous()
         dh = self._hbuf("dh", B, H2)
         L.linear_cls_bwd(dl, h, H2, A("final_hierarchical_all.weight"), A("final_hierarchical_all.weight", "g"),
                          A("final_hierarchical_all.bias", "g"), dh, B, H2, self.n_classes, 0.0, 0, L.F32)

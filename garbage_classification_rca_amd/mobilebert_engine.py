@@ -21,20 +21,23 @@ position table (position[t] + token_type[0]) and ``mmrca_linear_cls_*`` are the 
 in front of a NoNorm its bias gradient (gamma * column sums of dy), so no bias column-sum pass runs for those.
 
 Arena:  text_model.mobilebert.* (transformers' order; NoNorm registers bias before weight) | head.weight [C, 512] | head.bias.
-Same ``forward`` / ``backward`` / ``trainable_spans`` / ``groups`` contract as ``ClassifierEngine``, so the flat optimizers,
-``GradSync``, ``hip_train_step`` and ``GraphedTrainStep`` drive it unchanged.  Compute modes: fp32 (the compliant one) and bf16.
+``MobileBertEngine`` derives from ``ClassifierEngine``: ``forward`` / ``backward`` / ``trainable_spans`` and the linear head are that
+class's, and this one supplies its spec checks, ``_text_entries``, ``_group_of``, ``init_parameters`` and the encoder
+(``_encoder_forward`` / ``_encoder_backward``).  So the flat optimizers, ``GradSync``, ``hip_train_step`` and ``GraphedTrainStep`` drive
+it unchanged.  Compute modes: fp32 (the compliant one) and bf16.
 """
 from __future__ import annotations
 
 import math
 import re
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional
 
 import torch
 
 from . import lib as L
-from .engine import Arena, MMRCAEngine, ROWPAD, TextPack, _round_up
+from .classifier_engine import ClassifierEngine
+from .engine import ROWPAD, TextPack, _round_up, parse_dtype
 
 
 @dataclass(frozen=True)
@@ -99,8 +102,11 @@ def mobilebert_params(s: MobileBertSpec):
     return ents
 
 
-class MobileBertEngine(MMRCAEngine):
-    """Owns parameters, gradients and activations of one MobileBERT classifier replica on one GPU."""
+class MobileBertEngine(ClassifierEngine):
+    """Owns parameters, gradients and activations of one MobileBERT classifier replica on one GPU: ``ClassifierEngine``'s step and
+    head around this class's encoder."""
+
+    ENCODER_WORD = "encoder"
 
     def __init__(self, n_classes: int = 4, dtype="fp32", device="cuda", spec: MobileBertSpec = MOBILEBERT,
                  gemm_impl: int = L.IMPL_AUTO, attn_impl: int = L.IMPL_AUTO):
@@ -109,51 +115,22 @@ class MobileBertEngine(MMRCAEngine):
         here contracts over 128 or 512 on a few dozen to a few thousand rows, shapes the three-pass kernels do not take (DESIGN K9
         has the measured breakdown of a step)."""
         L.load()
-        if isinstance(dtype, str):
-            name = dtype.lower()
-            if name not in ("fp32", "f32", "bf16"):
-                raise ValueError(f"MobileBERT runs in {' or '.join(MODES)}, not {dtype!r} (the split-bf16 modes are not built for this model)")
-            dtype = torch.bfloat16 if name == "bf16" else torch.float32
-        if dtype not in (torch.float32, torch.bfloat16):
+        if isinstance(dtype, str) and dtype.lower() not in ("fp32", "f32", "bf16"):
+            raise ValueError(f"MobileBERT runs in {' or '.join(MODES)}, not {dtype!r} (the split-bf16 modes are not built for this model)")
+        mode_flags = parse_dtype(dtype)
+        if mode_flags[0] not in (torch.float32, torch.bfloat16):
             raise ValueError(f"MobileBERT runs in {' or '.join(MODES)}, not {dtype}")
         s = spec
         if s.inner % s.heads or (s.inner // s.heads) % 4 or s.inner // s.heads > 128:
             raise ValueError("head dim must be a multiple of 4, at most 128")
-        self.kind, self.backbone, self.ts, self.vs, self.conv = "text", s.name, s, None, None
-        self.x3 = self.x3f = False
-        self.n_classes, self.reverse, self.mode = int(n_classes), True, 0
-        if not 1 <= self.n_classes <= 16:
+        self.kind, self.backbone = "text", s.name
+        if not 1 <= int(n_classes) <= 16:
             raise ValueError(f"n_classes must be in [1, 16], got {n_classes}")
-        self.dtype, self.device = dtype, torch.device(device)
-        self.dt = self.bdt = L.dtype_code(dtype)
-        self.gdtype, self.conv_dtype = dtype, None
-        self.gemm_impl, self.attn_impl = gemm_impl, attn_impl
-        self.feat_dim = self.d_txt = s.dim
-        self.d_img = 0
-        enc = mobilebert_params(s)
-        ents = [("text_model." + k, shp) for k, shp in enc]
-        self.head_keys = [("head.weight", (self.n_classes, s.dim)), ("head.bias", (self.n_classes,))]
-        ents += self.head_keys
-        self.arena = Arena(ents, self.device, with_lp=(dtype == torch.bfloat16))
-        self.param_keys = [k for k, _ in ents]
-        self.encoder_span = self.arena.span(ents[0][0], "text_model." + enc[-1][0])
-        self.head_span = self.arena.span("head.weight", "head.bias")
-        self._bufs: Dict[Tuple, torch.Tensor] = {}
-        self._g_planes = self._ln_planes = False
-        self._plane_valid, self._plane_fresh = set(), set()
-        self._saved = None
-        self.groups: Dict[str, Tuple[int, int]] = {}
-        starts = []
-        for k in self.param_keys:
-            gname = self._group_of(k)
-            if not starts or starts[-1][0] != gname:
-                starts.append((gname, self.arena.offsets[k][0]))
-        for j, (gname, lo) in enumerate(starts):
-            hi = starts[j + 1][1] if j + 1 < len(starts) else self.arena.total
-            self.groups[gname] = (lo, hi)
-        self.grad_sync = None
-        self._side_v = self._side_t = self._side = None
-        self._text_stream = None
+        self.reverse, self.mode = True, 0
+        self._build(mode_flags, device, int(n_classes), gemm_impl, attn_impl, s)
+
+    def _text_entries(self):
+        return mobilebert_params(self.ts)
 
     @staticmethod
     def _group_of(key: str) -> str:
@@ -210,7 +187,9 @@ class MobileBertEngine(MMRCAEngine):
                      self.G(bias_key + ".bias"), ws, M, D, D, D, D, D, self.dt)
 
     # ------------------------------------------------------------------ encoder
-    def _encoder_forward(self, ids, mask, save, drop_p, drop_seed, pack: Optional[TextPack], taps=None):
+    def _encoder_forward(self, ids, mask, images, save, drop_p, drop_seed, pack: Optional[TextPack], bn_train=False, taps=None):
+        """drop_p: the attention-probability dropout (0.1 in train mode; the model has no other).  taps: ``hidden_states`` indices n in
+        [1, layers] whose class-token rows [B, 512] come back as ``saved["taps"][n]`` (``last_taps`` after a ``forward``)."""
         s, P = self.ts, "text_model."
         B, T = ids.shape
         if T > s.max_pos:
@@ -342,45 +321,3 @@ class MobileBertEngine(MMRCAEngine):
         L.embed_bwd(ds0, sv["pos"], sv["zeros"], self.G(Ek + "position_embeddings.weight"), self.G(Ek + "token_type_embeddings.weight"),
                     None, M, D, self.dt)
         self._ready("text_emb", flush=True)
-
-    # ------------------------------------------------------------------ whole model
-    def forward(self, ids, mask, images=None, drop_p: float = 0.0, seed: int = 0, save: bool = True, enc_drop_p: float = 0.0,
-                text_pack: Optional[TextPack] = None, bn_train: bool = False, taps=None):
-        """ids / mask int64 [B, T] in HBM -> logits fp32 [B, n_classes].  drop_p: dropout in front of the classifier (the model has
-        none: 0); enc_drop_p: the attention-probability dropout (0.1 in train mode).  taps: ``hidden_states`` indices n in [1, layers]
-        whose class-token rows [B, 512] are kept as ``last_taps[n]``."""
-        for t, nm in ((ids, "input ids"), (mask, "attention mask")):
-            if t is None or not t.is_cuda:
-                raise L.MmrcaError(f"{nm} must be in HBM; the classifier path has no CPU fallback")
-        self.refresh_working_copy()
-        feat, esv = self._encoder_forward(ids, mask, save, enc_drop_p, int(seed), text_pack, taps)
-        self.last_taps = esv["taps"]
-        B = feat.shape[0]
-        logits = torch.empty(B, self.n_classes, dtype=torch.float32, device=self.device)
-        head_seed = self._site_seed(int(seed), 255, 0)
-        L.linear_cls_fwd(feat, feat.stride(0), self.arena.view("head.weight"), self.arena.view("head.bias"), logits, B, self.feat_dim,
-                         self.n_classes, float(drop_p), head_seed, self.dt)
-        self._saved = dict(B=B, feat=feat, enc=esv, drop_p=float(drop_p), seed=head_seed, full=save)
-        return logits
-
-    def backward(self, dlogits, train_text: bool = True, train_image: bool = True):
-        """accumulates into the gradient arena: the head always, the encoder when train_text is set"""
-        sv = self._saved
-        if sv is None:
-            raise L.MmrcaError("backward() without a forward()")
-        train_enc = bool(train_text)
-        if train_enc and not sv["full"]:
-            raise L.MmrcaError("backward through the encoder needs forward(save=True)")
-        B, feat = sv["B"], sv["feat"]
-        dl = dlogits.to(torch.float32).contiguous()
-        dfeat = torch.empty(B, self.feat_dim, dtype=feat.dtype, device=self.device) if train_enc else None
-        L.linear_cls_bwd(dl, feat, feat.stride(0), self.arena.view("head.weight"), self.arena.view("head.weight", "g"),
-                         self.arena.view("head.bias", "g"), dfeat, B, self.feat_dim, self.n_classes, sv["drop_p"], sv["seed"], self.dt)
-        self._ready("head", flush=not train_enc)
-        if train_enc:
-            self._encoder_backward(dfeat, sv["enc"])
-        self.arena.lp_valid = False
-
-    def trainable_spans(self, train_text: bool, train_image: bool = False):
-        """[lo, hi) slices an optimizer step / all-reduce covers: the whole arena, or the head alone while the encoder is frozen"""
-        return [(0, self.arena.total)] if train_text else [(self.groups["head"][0], self.arena.total)]

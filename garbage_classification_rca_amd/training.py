@@ -125,7 +125,7 @@ class GraphedTrainStep:
         self._graphs, self._eager_left, self._no_graph = {}, {}, set()
         self._epoch = torch.zeros(1, dtype=torch.int64, device=model.engine.device)
         self.replays = 0
-        self._generation = getattr(model.engine, "buffer_generation", 0)
+        self._generation = model.engine.buffer_generation
         L.seed_epoch_set(0)                    # resolves the epoch words' addresses outside any capture
 
     def _sync_in_graph(self):
@@ -142,10 +142,10 @@ class GraphedTrainStep:
         in_graph = self._sync_in_graph()
         key = (tuple(ids.shape), tuple(images.shape), images.dtype, labels.dtype, tt, ti, bool(model.training),
                float(model.drop_ratio), float(model.enc_dropout), bool(do_step) if in_graph else None)
-        if getattr(eng, "buffer_generation", 0) != self._generation:       # engine.release_buffers() freed what the graphs point into
+        if eng.buffer_generation != self._generation:       # engine.release_buffers() freed what the graphs point into
             self._graphs.clear()
             self._eager_left.clear()
-            self._generation = getattr(eng, "buffer_generation", 0)
+            self._generation = eng.buffer_generation
         ent = self._graphs.get(key)
         if ent is None and key not in self._no_graph and not self._eager() and self._eager_left.setdefault(key, self.warmup) <= 0:
             try:
