@@ -40,12 +40,17 @@ class Transforms:
     Resize(INTER_LINEAR: half-pixel centres, no antialiasing, uint8 result) -> ImageNet mean/std.  This is the per-sample
     DataLoader-worker form; ``preprocess.GpuImagePipeline`` is the same arithmetic as one GPU launch per batch.  Of the
     training augmentations (albumentations, :407-429) only the vertical / horizontal flips with
-    probability ``prob_aug`` are applied."""
+    probability ``prob_aug`` are applied.  ``mean`` / ``std``: per-channel constants instead of ImageNet's (main_image.py
+    --calculate_dataset_stats)."""
     MEAN = torch.tensor([0.485, 0.456, 0.406]).view(3, 1, 1)
     STD = torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
 
-    def __init__(self, width, height, train=False, prob_aug=0.0):
+    def __init__(self, width, height, train=False, prob_aug=0.0, mean=None, std=None):
         self.width, self.height, self.train, self.prob_aug = width, height, train, prob_aug
+        if mean is not None:
+            self.MEAN = torch.tensor([float(v) for v in mean]).view(3, 1, 1)
+        if std is not None:
+            self.STD = torch.tensor([float(v) for v in std]).view(3, 1, 1)
 
     def __call__(self, img):
         from .preprocess import plan_padding

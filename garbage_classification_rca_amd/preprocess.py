@@ -183,9 +183,11 @@ def _pinned_no_fork(nbytes: int) -> torch.Tensor:
 class GpuImagePipeline:
     """Reusable staging for batches of up to ``max_batch`` images of at most ``max_pixels`` pixels each.  Two pinned host
     buffers and two device buffers alternate, the copy runs on its own stream, so batch i+1 can be staged and copied
-    while batch i is being consumed (``__call__`` returns a tensor that is ordered on the caller's current stream)."""
+    while batch i is being consumed (``__call__`` returns a tensor that is ordered on the caller's current stream).
+    ``mean`` / ``std``: the per-channel constants of A.Normalize (default: ImageNet's; main_image.py --calculate_dataset_stats
+    passes the training set's)."""
 
-    def __init__(self, out_h: int, out_w: int, max_batch: int, max_pixels: int, device="cuda"):
+    def __init__(self, out_h: int, out_w: int, max_batch: int, max_pixels: int, device="cuda", mean=MEAN, std=STD):
         self.out_h, self.out_w, self.max_batch = int(out_h), int(out_w), int(max_batch)
         self.device = torch.device(device)
         self.max_pixels = int(max_pixels)
@@ -203,8 +205,8 @@ class GpuImagePipeline:
         self._slot_free = [None, None]          # event: the kernel that consumed this slot has finished
         self._keep = [None, None]               # pinned batch a slot's H2D copy reads from (kept alive until the slot is reused)
         self._i = 0
-        self._mean = (C.c_float * 3)(*MEAN)
-        self._std = (C.c_float * 3)(*STD)
+        self._mean = (C.c_float * 3)(*(float(v) for v in mean))
+        self._std = (C.c_float * 3)(*(float(v) for v in std))
         # One tiny batch through every stage NOW: loads the kernels' code objects and makes every device allocation before the
         # caller forks its DataLoader workers (the first launch from a process with 16 live forked children took 20 s on the
         # MI355X box; after this warm-up every call is ~10 ms).
@@ -214,10 +216,10 @@ class GpuImagePipeline:
         self([tiny])
         torch.cuda.synchronize(self.device)
 
-    def __call__(self, images: Sequence[np.ndarray], flips: Optional[Sequence[Tuple[bool, bool]]] = None,
-                 aug: Optional[Sequence[dict]] = None) -> torch.Tensor:
-        """images: decoded uint8 HWC arrays (or tensors).  flips: (vertical, horizontal) per image (validation pipeline +
-        flips in one launch).  aug: one ``sample_train_params`` dict per image -> the full TRAIN_PIPELINE."""
+    def _stage(self, images, flips=None, aug=None, pad: bool = True):
+        """The staging half of a call: take the next slot, write images and descriptors into its pinned buffers, start the
+        H2D copies on the copy stream and order the caller's stream after them.  -> (slot, B, bytes of the rotate
+        descriptors, any rotation enabled); ``_release(slot)`` after the kernels that read the slot are launched."""
         packed = images if isinstance(images, dict) else None           # pack_images() output: already in the staging layout
         shapes = [tuple(x) for x in packed["shapes"].tolist()] if packed is not None else [(int(im.shape[0]), int(im.shape[1])) for im in images]
         B = len(shapes)
@@ -274,7 +276,7 @@ class GpuImagePipeline:
                     o, h, w = off, dh, dw
                     off += (dh * dw * 3 + 15) // 16 * 16
                     any_rot = True
-            pt, pl, ph, pw = plan_padding(h, w, ar)
+            pt, pl, ph, pw = plan_padding(h, w, ar) if pad else (0, 0, h, w)
             fv, fh = (flips[b] if flips is not None else (False, False))
             desc[b] = (o, h, w, pt, pl, ph, pw, int(fv), int(fh))
             if aug is not None:
@@ -306,6 +308,30 @@ class GpuImagePipeline:
             if aug is not None:
                 self._dev_aug[k][:nr + na].copy_(self._host_aug[k][:nr + na], non_blocking=True)
         main.wait_stream(self._copy_stream)
+        return k, B, nr, any_rot
+
+    def _release(self, k: int):
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._slot_free[k] = ev
+
+    def moments(self, images, pad: bool = True) -> torch.Tensor:
+        """Per image and channel {sum v, sum v*v} (int64 [B, 3, 2], on the device) of the uint8 image that the resize stage
+        produces -- exact integers, the resized image is never written (csrc/preprocess.hip::image_stats_k).  ``images`` as
+        for ``__call__``.  pad=False: stretch resize without PadToMaintainAR (the reference's STATS_PIPELINE,
+        main_image.py:412-417)."""
+        k, B, _, _ = self._stage(images, pad=pad)
+        sums = torch.empty(B, 3, 2, dtype=torch.int64, device=self.device)     # (every sum is far below 2^63: uint64 read as int64)
+        L._check(L.load().mmrca_image_stats_u8(L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(sums), B, self.out_h, self.out_w,
+                                               L.stream_ptr()), "mmrca_image_stats_u8")
+        self._release(k)
+        return sums
+
+    def __call__(self, images: Sequence[np.ndarray], flips: Optional[Sequence[Tuple[bool, bool]]] = None,
+                 aug: Optional[Sequence[dict]] = None) -> torch.Tensor:
+        """images: decoded uint8 HWC arrays (or tensors).  flips: (vertical, horizontal) per image (validation pipeline +
+        flips in one launch).  aug: one ``sample_train_params`` dict per image -> the full TRAIN_PIPELINE."""
+        k, B, nr, any_rot = self._stage(images, flips, aug)
         out = torch.empty(B, 3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
         lib = L.load()
         mean, std = C.cast(self._mean, C.c_void_p), C.cast(self._std, C.c_void_p)
@@ -320,7 +346,5 @@ class GpuImagePipeline:
                                                self.out_w, L.stream_ptr()), "mmrca_image_resize_u8")
             L._check(lib.mmrca_image_augment(L.ptr(self._u8[0]), L.ptr(self._u8[1]), self._dev_aug[k].data_ptr() + nr, L.ptr(out), B,
                                              self.out_h, self.out_w, mean, std, L.stream_ptr()), "mmrca_image_augment")
-        ev = torch.cuda.Event()
-        ev.record(main)
-        self._slot_free[k] = ev
+        self._release(k)
         return out

@@ -138,7 +138,7 @@ def train(kind, argv, build_model, batch_table):
     for flag, default in (("use_synonyms", False), ("prob_aug_text", 0.6)):
         if getattr(args, flag, default) != default:
             print("WARNING: --{} is accepted for CLI compatibility but not implemented on this path (SURVEY.md section 2: out of scope)".format(flag))
-    if args.calculate_dataset_stats:
+    if args.calculate_dataset_stats and kind != "image":
         print("WARNING: --calculate_dataset_stats is accepted for CLI compatibility; the ImageNet mean / std are used, as in main_both.py")
 
     train_path = "_".join([args.dataset_folder_name, TRAIN_DATASET_PATH])
@@ -150,12 +150,20 @@ def train(kind, argv, build_model, batch_table):
         from .main_both import DecodeOnly, Transforms, collate_decoded
         WIDTH, HEIGHT = global_model.get_image_size()
         gpu_pre = bool(args.gpu_preprocess)
-        train_data = CustomImageTextFolder(root=train_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT, True, args.prob_aug))
-        val_data = CustomImageTextFolder(root=val_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT))
+        norm = {}           # A.Normalize constants for the train and validation pipelines; empty = ImageNet's
+        if args.calculate_dataset_stats:
+            # main_image.py:425-437: the training set's own statistics at the model's input size, STATS_PIPELINE = stretch resize
+            from . import dataset_stats
+            print("Calculating Train Dataset statistics...")
+            sums, batch_sizes = dataset_stats.compute(train_path, WIDTH, HEIGHT, device, pad=False, seed=args.seed, num_workers=args.num_workers)
+            mean_train, std_train = dataset_stats.report(sums, batch_sizes, WIDTH * HEIGHT)
+            norm = dict(mean=mean_train, std=std_train)
+        train_data = CustomImageTextFolder(root=train_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT, True, args.prob_aug, **norm))
+        val_data = CustomImageTextFolder(root=val_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT, **norm))
         if gpu_pre:
             # the reference's TRAIN_PIPELINE / VALIDATION_PIPELINE (main_image.py:409-446) are main_both.py's lists
             from .preprocess import GpuImagePipeline, sample_train_params
-            image_pipeline = GpuImagePipeline(HEIGHT, WIDTH, max_batch=max(_batch_size, _batch_size_FT), max_pixels=640 * 480, device=device)
+            image_pipeline = GpuImagePipeline(HEIGHT, WIDTH, max_batch=max(_batch_size, _batch_size_FT), max_pixels=640 * 480, device=device, **norm)
             aug_rng = np.random.default_rng(None if args.seed is None else int(args.seed) + 7919)
             aug_params = lambda n: sample_train_params(aug_rng, n, args.prob_aug)      # noqa: E731
             collate = collate_decoded

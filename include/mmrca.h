@@ -614,6 +614,14 @@ int mmrca_image_rotate_crop(void* staging, const void* desc /* MmrcaRotateDesc[B
 /* PadToMaintainAR + Resize only (no flips, no normalisation): uint8 [B, out_h, out_w, 3] for the stages below */
 int mmrca_image_resize_u8(const void* staging, const void* desc /* MmrcaImageDesc[B] */, void* out_u8, int B, int out_h, int out_w,
                           void* stream);
+/* Dataset statistics (main_image.py:212-235, calculate_mean_std_train_dataset): for every image the integer moments of the
+ * uint8 image that mmrca_image_resize_u8 would write for the same descriptor and output size -- sums[b][c] = {sum v, sum v*v}
+ * over its out_h x out_w pixels -- without writing that image.  Integer accumulation only, so the result is exact and
+ * independent of the launch shape; the call clears `sums` itself.  A thread accumulates in 32 bits: at most 66051 pixels
+ * per thread (65025 x pixels < 2^32), which the call checks.  The flip fields do not change the sums and are ignored. */
+int mmrca_image_stats_u8(const void* staging, const void* desc /* MmrcaImageDesc[B], device */,
+                         void* sums /* uint64 [B][3][2] device: per image, per channel, {sum v, sum v*v} */,
+                         int B, int out_h, int out_w, void* stream);
 typedef struct {
   float blur[7];             /* 1-D Gaussian taps; the 2-D weight is blur[i] * blur[j] */
   int32_t blur_k;            /* 0 = off, else 3 / 5 / 7 */
