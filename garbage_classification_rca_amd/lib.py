@@ -231,6 +231,14 @@ GEMM_PROFILE = None     # bench.py sets this to a list: every MFMA-qualified GEM
 KERNEL_PROFILE = None   # bench.py sets this to a list: (kind, meta, start event, end event) of attention / head launches
 
 
+def _events():
+    """the bracket of one profiled launch: two timing events, the first recorded on the current stream now; the caller records the
+    second behind the launch.  Only ever called while one of the profile lists is on."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0, e1
+
+
 class _Bracket:
     """HIP events around one launch on the current stream, recorded only while bench.py's replay asks for them."""
 
@@ -239,8 +247,7 @@ class _Bracket:
 
     def __enter__(self):
         if self.on:
-            self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.e0.record()
+            self.e0, self.e1 = _events()
         return self
 
     def __exit__(self, *exc):
@@ -301,8 +308,7 @@ def gemm(A, B, Cout, *, bias=None, addend=None, preact=None, M, N, K, lda, ldb, 
     prof = GEMM_PROFILE is not None and (gemm_is_mfma(M, N, K, a_layout, dtype, impl) or (dtype == F32 and impl != IMPL_REF))
     timed = prof or CONV_PROFILE is not None      # the conv step's byte table times EVERY GEMM (ragged / general-kernel shapes too)
     if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        e0, e1 = _events()
     if colsum is not None:
         if accum:
             raise MmrcaError("gemm: colsum is not available in accumulate mode")
@@ -343,8 +349,7 @@ def gemm_splitk(A, B, Cout, workspace, *, M, N, K, lda, ldb, ldc, a_layout=KROW,
     _dev(A, "gemm_splitk A")
     prof = GEMM_PROFILE is not None
     if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        e0, e1 = _events()
     _check(load().mmrca_gemm_splitk(ptr(A), ptr(B), ptr(Cout), ptr(workspace), workspace.numel() * workspace.element_size(),
                                     M, N, K, lda, ldb, ldc, a_layout, b_layout, stream_ptr()), "mmrca_gemm_splitk")
     if prof:
@@ -363,8 +368,7 @@ def gemm_x3(A, B, Cout, *, C_lo=None, bias=None, addend=None, preact=None, colsu
         streamk_workspace(M, N, A[0].device)
     prof = GEMM_PROFILE is not None
     if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        e0, e1 = _events()
     _check(load().mmrca_gemm_x3(ptr(A[0]), ptr(A[1]), ptr(B[0]), ptr(B[1]), ptr(Cout), ptr(C_lo), ptr(bias), ptr(addend), ptr(preact),
                                 ptr(colsum), M, N, K, lda, ldb, ldc, a_layout, b_layout, act, int(accum), impl, stream_ptr()),
            "mmrca_gemm_x3")
@@ -380,8 +384,7 @@ def gemm_splitk_x3(A, B, Cout, workspace, *, M, N, K, lda, ldb, ldc, a_layout=KR
     _dev(A[0], "gemm_splitk_x3 A")
     prof = GEMM_PROFILE is not None
     if prof:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        e0, e1 = _events()
     _check(load().mmrca_gemm_splitk_x3(ptr(A[0]), ptr(A[1]), ptr(B[0]), ptr(B[1]), ptr(Cout), ptr(workspace),
                                        workspace.numel() * workspace.element_size(), M, N, K, lda, ldb, ldc, a_layout, b_layout,
                                        stream_ptr()), "mmrca_gemm_splitk_x3")
@@ -794,69 +797,96 @@ def _out_hw(H, W, s):
     return (H - 1) // s + 1, (W - 1) // s + 1
 
 
-def _patch_bytes(a):          # (x, col, B, H, W, C, stride, ldk, dtype): the input rows once + the patch matrix once
-    Ho, Wo = _out_hw(a[3], a[4], a[6])
-    return (a[2] * a[3] * a[4] * a[5] + a[2] * Ho * Wo * a[7]) * _esz(a[8])
+def _pixels(a, stride=None):      # output pixels of a padded 3x3 / 5x5 window walk over a.H x a.W
+    Ho, Wo = _out_hw(a.H, a.W, a.stride if stride is None else stride)
+    return Ho * Wo
 
 
-def _dw_bwd_bytes(a):         # (dy, x, w, dx, dw, B, H, W, C, stride, dtype, ...): dy (output rows) + x + dx (input rows)
-    Ho, Wo = _out_hw(a[6], a[7], a[9])
-    return a[5] * a[8] * (Ho * Wo + 2 * a[6] * a[7]) * _esz(a[10])
+def _patch_bytes(a):          # the input rows once + the patch matrix once
+    return (a.B * a.H * a.W * a.C + a.B * _pixels(a) * a.ldk) * _esz(a.dtype)
 
 
-def _dw5_bwd_bytes(a):        # (dy, x, w, dx, dw, ...): dy once, plus x for the weight gradient, plus dx written
-    Ho, Wo = _out_hw(a[6], a[7], a[9])
-    return a[5] * a[8] * (Ho * Wo + (a[6] * a[7] if a[4] else 0) + (a[6] * a[7] if a[3] else 0)) * _esz(a[10])
+def _dw_fwd_bytes(a):         # x (input rows) + y (output rows)
+    return a.B * a.C * (a.H * a.W + _pixels(a)) * _esz(a.dtype)
+
+
+def _dw_bwd_bytes(a):         # dy (output rows) + x + dx (input rows)
+    return a.B * a.C * (_pixels(a) + 2 * a.H * a.W) * _esz(a.dtype)
+
+
+def _dw5_bwd_bytes(a):        # dy once, plus x for the weight gradient, plus dx written
+    return a.B * a.C * (_pixels(a) + (a.H * a.W if a.dw else 0) + (a.H * a.W if a.dx else 0)) * _esz(a.dtype)
+
+
+def _maxpool_bytes(a):        # the input-sized tensor, the pooled tensor and the uint8 argmax taps
+    return a.B * a.C * (a.H * a.W * _esz(a.dtype) + _pixels(a, 2) * (_esz(a.dtype) + 1))
 
 
 # ALGORITHMIC HBM bytes of one launch (every operand the op must read once + every result it must write once, per-channel
-# vectors ignored), from the launch arguments: the byte roofline of the conv step in bench.py
+# vectors ignored), from the launch arguments under their names in include/mmrca.h (a.rows, a.C, a.dtype, ...; a pointer is its
+# integer handle or None): the byte roofline of the conv step in bench.py
 _CONV_BYTES = {
-    "mmrca_nchw_to_rows": ("layout", lambda a: a[2] * a[3] * a[4] * a[5] * (4 + _esz(a[6]))),
+    "mmrca_nchw_to_rows": ("layout", lambda a: a.B * a.C * a.H * a.W * (4 + _esz(a.dtype))),
     "mmrca_im2row3x3": ("patches", _patch_bytes), "mmrca_col2im3x3": ("patches", _patch_bytes),
     "mmrca_im2row3x3_tap": ("patches", _patch_bytes), "mmrca_col2im3x3_tap": ("patches", _patch_bytes),
-    "mmrca_dwconv3x3_fwd": ("depthwise", lambda a: a[3] * a[6] * (a[4] * a[5] + _out_hw(a[4], a[5], a[7])[0] * _out_hw(a[4], a[5], a[7])[1]) * _esz(a[8])),
+    "mmrca_dwconv3x3_fwd": ("depthwise", _dw_fwd_bytes),
     "mmrca_dwconv3x3_bwd": ("depthwise", _dw_bwd_bytes), "mmrca_dwconv3x3_bwd_ws": ("depthwise", _dw_bwd_bytes),
-    "mmrca_dwconv5x5_fwd": ("depthwise 5x5", lambda a: a[3] * a[6] * (a[4] * a[5] + _out_hw(a[4], a[5], a[7])[0] * _out_hw(a[4], a[5], a[7])[1]) * _esz(a[8])),
-    "mmrca_dwconv5x5_bwd_ws": ("depthwise 5x5", lambda a: _dw5_bwd_bytes(a)),
-    "mmrca_conv3x3_fwd": ("conv3x3 implicit GEMM", lambda a: (a[6] * a[7] * a[8] * (a[9] + a[10]) + 9 * a[9] * a[10]) * _esz(a[11])),
-    "mmrca_conv3x3_wgrad": ("conv3x3 implicit GEMM", lambda a: a[3] * a[4] * a[5] * (a[6] + a[7]) * _esz(a[8]) + 9 * a[6] * a[7] * 4),
-    "mmrca_gemm_bnstats": ("GEMM (1x1 / patch)", lambda a: (a[3] * a[5] + a[4] * a[5] + a[3] * a[4]) * _esz(a[9])),
-    "mmrca_channel_interleave2": ("layout", lambda a: 2 * a[4] * 2 * a[5] * _esz(a[6])),
-    "mmrca_channel_deinterleave2": ("layout", lambda a: 2 * a[4] * 2 * a[5] * _esz(a[6])),
-    "mmrca_bn_stats": ("BatchNorm", lambda a: a[5] * a[6] * _esz(a[11]) if a[10] else 0),
-    "mmrca_bn_stats_ws": ("BatchNorm", lambda a: a[5] * a[6] * _esz(a[11]) if a[10] else 0),
-    "mmrca_bn_stats_fused": ("BatchNorm", lambda a: a[5] * a[6] * _esz(a[10])),
-    "mmrca_bn_act_fwd": ("BatchNorm", lambda a: 2 * a[6] * a[7] * _esz(a[9])),
-    "mmrca_bn_act_fwd_res": ("BatchNorm", lambda a: 3 * a[8] * a[9] * _esz(a[12])),
-    "mmrca_bn_moments": ("BatchNorm", lambda a: a[4] * a[5] * _esz(a[7])),
-    "mmrca_bn_act_fwd_fin": ("BatchNorm", lambda a: (3 if a[6] else 2) * a[13] * a[14] * _esz(a[19])),
+    "mmrca_dwconv5x5_fwd": ("depthwise 5x5", _dw_fwd_bytes),
+    "mmrca_dwconv5x5_bwd_ws": ("depthwise 5x5", _dw5_bwd_bytes),
+    "mmrca_conv3x3_fwd": ("conv3x3 implicit GEMM", lambda a: (a.B * a.H * a.W * (a.Cin + a.Cout) + 9 * a.Cin * a.Cout) * _esz(a.dtype)),
+    "mmrca_conv3x3_wgrad": ("conv3x3 implicit GEMM", lambda a: a.B * a.H * a.W * (a.Cin + a.Cout) * _esz(a.dtype) + 9 * a.Cin * a.Cout * 4),
+    "mmrca_gemm_bnstats": ("GEMM (1x1 / patch)", lambda a: (a.M * a.K + a.N * a.K + a.M * a.N) * _esz(a.dtype)),
+    "mmrca_channel_interleave2": ("layout", lambda a: 2 * a.rows * 2 * a.bf * _esz(a.dtype)),
+    "mmrca_channel_deinterleave2": ("layout", lambda a: 2 * a.rows * 2 * a.bf * _esz(a.dtype)),
+    "mmrca_bn_stats": ("BatchNorm", lambda a: a.rows * a.C * _esz(a.dtype) if a.train else 0),
+    "mmrca_bn_stats_ws": ("BatchNorm", lambda a: a.rows * a.C * _esz(a.dtype) if a.train else 0),
+    "mmrca_bn_stats_fused": ("BatchNorm", lambda a: a.rows * a.C * _esz(a.dtype)),
+    "mmrca_bn_act_fwd": ("BatchNorm", lambda a: 2 * a.rows * a.C * _esz(a.dtype)),
+    "mmrca_bn_act_fwd_res": ("BatchNorm", lambda a: 3 * a.rows * a.C * _esz(a.dtype)),
+    "mmrca_bn_moments": ("BatchNorm", lambda a: a.rows * a.C * _esz(a.dtype)),
+    "mmrca_bn_act_fwd_fin": ("BatchNorm", lambda a: (3 if a.res else 2) * a.rows * a.C * _esz(a.dtype)),
     # backward with batch statistics: the sums need dy and z once, the apply pass needs them again and writes dx
-    "mmrca_bn_act_bwd": ("BatchNorm", lambda a: (5 if a[13] else 3) * a[10] * a[11] * _esz(a[14])),
-    "mmrca_bn_act_bwd_ws": ("BatchNorm", lambda a: (5 if a[13] else 3) * a[10] * a[11] * _esz(a[14])),
-    "mmrca_bn_act_bwd_sums": ("BatchNorm", lambda a: 3 * a[10] * a[11] * _esz(a[14])),
-    "mmrca_rowpool_mean": ("pool / squeeze-excitation", lambda a: a[2] * a[3] * a[4] * _esz(a[5])),
-    "mmrca_rowpool_mean_bwd": ("pool / squeeze-excitation", lambda a: a[2] * a[3] * a[4] * _esz(a[6]) * (2 if a[5] else 1)),
-    "mmrca_se_scale_fwd": ("pool / squeeze-excitation", lambda a: 2 * a[3] * a[4] * a[5] * _esz(a[6])),
-    "mmrca_se_mlp_fwd": ("pool / squeeze-excitation", lambda a: (2 * a[10] * a[11] + 3 * a[9] * (a[10] + a[11])) * _esz(a[12])),
-    "mmrca_se_mlp_bwd": ("pool / squeeze-excitation", lambda a: (2 * a[17] * a[18] + 6 * a[16] * (a[17] + a[18])) * _esz(a[19]) + 2 * a[17] * a[18] * 4),
-    "mmrca_se_scale_bwd": ("pool / squeeze-excitation", lambda a: (3 if a[3] else 2) * a[5] * a[6] * a[7] * _esz(a[8])),
-    "mmrca_se_dx": ("pool / squeeze-excitation", lambda a: (3 if a[8] else 2) * a[4] * a[5] * a[6] * _esz(a[7])),
-    "mmrca_residual_add": ("residual", lambda a: (3 if a[0] else 2) * a[4] * a[5] * _esz(a[6])),
-    "mmrca_maxpool3x3s2_fwd": ("pool / squeeze-excitation", lambda a: a[3] * a[6] * (a[4] * a[5] * _esz(a[7]) + _out_hw(a[4], a[5], 2)[0] * _out_hw(a[4], a[5], 2)[1] * (_esz(a[7]) + 1))),
-    "mmrca_maxpool3x3s2_bwd": ("pool / squeeze-excitation", lambda a: a[3] * a[6] * (a[4] * a[5] * _esz(a[7]) + _out_hw(a[4], a[5], 2)[0] * _out_hw(a[4], a[5], 2)[1] * (_esz(a[7]) + 1))),
-    "mmrca_channel_gather": ("layout", lambda a: 2 * a[3] * a[5] * _esz(a[8])),
+    "mmrca_bn_act_bwd": ("BatchNorm", lambda a: (5 if a.train else 3) * a.rows * a.C * _esz(a.dtype)),
+    "mmrca_bn_act_bwd_ws": ("BatchNorm", lambda a: (5 if a.train else 3) * a.rows * a.C * _esz(a.dtype)),
+    "mmrca_bn_act_bwd_sums": ("BatchNorm", lambda a: 3 * a.rows * a.C * _esz(a.dtype)),
+    "mmrca_rowpool_mean": ("pool / squeeze-excitation", lambda a: a.B * a.HW * a.C * _esz(a.dtype)),
+    "mmrca_rowpool_mean_bwd": ("pool / squeeze-excitation", lambda a: a.B * a.HW * a.C * _esz(a.dtype) * (2 if a.accumulate else 1)),
+    "mmrca_se_scale_fwd": ("pool / squeeze-excitation", lambda a: 2 * a.B * a.HW * a.C * _esz(a.dtype)),
+    "mmrca_se_mlp_fwd": ("pool / squeeze-excitation", lambda a: (2 * a.c * a.sq + 3 * a.B * (a.c + a.sq)) * _esz(a.dtype)),
+    "mmrca_se_mlp_bwd": ("pool / squeeze-excitation", lambda a: (2 * a.c * a.sq + 6 * a.B * (a.c + a.sq)) * _esz(a.dtype) + 2 * a.c * a.sq * 4),
+    "mmrca_se_scale_bwd": ("pool / squeeze-excitation", lambda a: (3 if a.dx else 2) * a.B * a.HW * a.C * _esz(a.dtype)),
+    "mmrca_se_dx": ("pool / squeeze-excitation", lambda a: (3 if a.z else 2) * a.B * a.HW * a.C * _esz(a.dtype)),
+    "mmrca_residual_add": ("residual", lambda a: (3 if a.a else 2) * a.B * a.per_sample * _esz(a.dtype)),
+    "mmrca_maxpool3x3s2_fwd": ("pool / squeeze-excitation", _maxpool_bytes),
+    "mmrca_maxpool3x3s2_bwd": ("pool / squeeze-excitation", _maxpool_bytes),
+    "mmrca_channel_gather": ("layout", lambda a: 2 * a.rows * a.Cout * _esz(a.dtype)),
 }
+
+
+_PARAM_NAMES = {}      # entry point -> parameter names of its prototype in include/mmrca.h; read at the first profiled launch
+
+
+def _named(name, args):
+    """the arguments of one launch under the header's parameter names (profiled launches only: the header is not read otherwise)"""
+    from types import SimpleNamespace
+    if not _PARAM_NAMES:
+        from . import abi
+        try:
+            protos = abi.prototypes()
+        except abi.MmrcaError as e:
+            raise MmrcaError(str(e)) from None
+        _PARAM_NAMES.update({fn: [pname for _, pname in params] for fn, (_, params) in protos.items()})
+    return SimpleNamespace(**dict(zip(_PARAM_NAMES[name], args)))
 
 
 def _c(name, *args):
     if CONV_PROFILE is not None:
         fam, fn = _CONV_BYTES.get(name, ("other", lambda a: 0))
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        named = _named(name, args)
+        e0, e1 = _events()
         _check(getattr(load(), name)(*args, stream_ptr()), name)
         e1.record()
-        CONV_PROFILE.append((fam, int(fn(args)), e0, e1))
+        CONV_PROFILE.append((fam, int(fn(named)), e0, e1))
         return
     _check(getattr(load(), name)(*args, stream_ptr()), name)
 

@@ -16,6 +16,12 @@
  *     accumulation and fp32 softmax/LayerNorm statistics (the benchmarked mode).
  *   - parameter gradients are always fp32 and are ACCUMULATED (+=) into the caller's gradient arena,
  *     which is what main_both.py:112-124 relies on for its sum-not-mean gradient accumulation.
+ *   - this header is also READ from Python (garbage_classification_rca_amd/abi.py: the tests hold lib.py's ctypes table and every
+ *     wrapper against it, the benchmark's byte table takes its argument names from it; what it cannot parse is an error), so
+ *     declarations keep to this grammar: one prototype per `;`, no macros and no function
+ *     pointers inside one; every parameter is named; scalar parameters are int, int64_t, uint64_t or float; anything with `*`
+ *     is a pointer (to void, char, float, an integer type above or int32_t, or a struct typedef'd here); the return type is int,
+ *     int64_t or const char*; enumerators carry explicit values; comments are block comments.
  *   - NO communication entry points, by decision (SURVEY section 8(b) sketched mmrca_comm_init / mmrca_allreduce /
  *     mmrca_comm_destroy): the one exchange step of the path -- the data-parallel gradient average that replaces
  *     nn.DataParallel, main_both.py:386-388 -- runs on RCCL through torch.distributed (backend "nccl"), one process per GPU,
