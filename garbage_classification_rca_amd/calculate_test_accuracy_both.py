@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from .CustomImageTextFolder import CustomImageTextFolder
-from .main_both import DecodeOnly, Transforms, collate_decoded
+from .main_both import Transforms, decode_only
 from .training import stage_images, trim_caption_columns
 from .multimodal_model import MM_RCA, Hierarchical, HierarchicalBimodalFusion
 from .options import args_parser
@@ -130,16 +130,16 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.model_path, map_location=device))
     model.eval()
     WIDTH, HEIGHT = model.get_image_size()
-    test_data = CustomImageTextFolder(root=args.dataset_folder_name, tokens_max_len=args.tokens_max_len or model.get_max_token_size(),
-                                      tokenizer_text=model.get_tokenizer(),
-                                      transform=DecodeOnly() if args.gpu_preprocess else Transforms(WIDTH, HEIGHT))
+    text_kw = dict(tokens_max_len=args.tokens_max_len or model.get_max_token_size(), tokenizer_text=model.get_tokenizer())
+    test_data, collate = decode_only(args.dataset_folder_name, **text_kw) if args.gpu_preprocess else \
+        (CustomImageTextFolder(root=args.dataset_folder_name, transform=Transforms(WIDTH, HEIGHT), **text_kw), None)
     print("Num of test samples: {}".format(len(test_data)))
     image_pipeline = None
     if args.gpu_preprocess:
         from .preprocess import GpuImagePipeline
         image_pipeline = GpuImagePipeline(HEIGHT, WIDTH, max_batch=_batch_size, max_pixels=640 * 480, device=device)
     loader = torch.utils.data.DataLoader(dataset=test_data, batch_size=_batch_size, shuffle=True, num_workers=min(8, args.num_workers),
-                                         pin_memory=True, collate_fn=collate_decoded if args.gpu_preprocess else None,
+                                         pin_memory=True, collate_fn=collate,
                                          multiprocessing_context="forkserver" if (args.gpu_preprocess and args.num_workers > 0) else None)
     acc, report, report_dict, cm = calculate_test_accuracy(model, loader, len(test_data), device, _batch_size,
                                                            mode_config_dict['both'], True, image_pipeline=image_pipeline)

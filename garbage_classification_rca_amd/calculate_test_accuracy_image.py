@@ -41,9 +41,10 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.model_path, map_location="cpu"))
     model.eval()
     WIDTH, HEIGHT = model.get_image_size()
-    from .main_both import DecodeOnly, Transforms, collate_decoded
+    from .main_both import Transforms, decode_only
     gpu_pre = bool(args.gpu_preprocess)
-    test_data = CustomImageTextFolder(root=args.dataset_folder_name, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT))
+    test_data, collate = decode_only(args.dataset_folder_name) if gpu_pre else \
+        (CustomImageTextFolder(root=args.dataset_folder_name, transform=Transforms(WIDTH, HEIGHT)), None)
     print("Num of test images: {}".format(len(test_data)))
     pipeline = None
     if gpu_pre:
@@ -51,7 +52,7 @@ def main(argv=None):
         pipeline = GpuImagePipeline(HEIGHT, WIDTH, max_batch=_batch_size, max_pixels=640 * 480, device=device)
     nw = min(8, args.num_workers)
     loader = torch.utils.data.DataLoader(test_data, batch_size=_batch_size, shuffle=False, num_workers=nw, pin_memory=True,
-                                         collate_fn=collate_decoded if gpu_pre else None,
+                                         collate_fn=collate,
                                          multiprocessing_context="forkserver" if (gpu_pre and nw > 0) else None)
     acc, report, report_dict, cm = calculate_test_accuracy(model, loader, len(test_data), device, _batch_size, pipeline)
     write_report(report_dict, cm, "image_model_{}_report_test_set_acc_{:.2f}.csv".format(args.image_model, acc),

@@ -1,0 +1,302 @@
+"""Baseline-JPEG decode for the GPU input path (C ABI: include/mmrca_jpeg.h).
+
+    file bytes --worker: mmrca_jpeg_entropy_decode (host C++)--> int16 coefficients --collate_jpeg: one flat tensor per batch-->
+    pinned --H2D--> mmrca_jpeg_idct_rgb (csrc/jpeg.hip) --> uint8 HWC RGB in the staging layout of preprocess.pack_images (device)
+
+The DataLoader workers do the bit-serial part (markers, Huffman) in libmmrca_jpeg.so, a host-only library that never touches the
+HIP runtime; dequantisation, inverse DCT, chroma upsampling and colour conversion are two launches per batch.  The decoded pixels
+never exist in host memory.  The result is byte-identical to ``PIL.Image.open(...).convert("RGB")`` of a libjpeg-turbo Pillow.
+Whatever the host decoder does not handle exactly (progressive, CMYK, odd samplings, damaged files, non-JPEG files) it DECLINES,
+and the worker decodes that one file with Pillow as ``main_both.DecodeOnly`` does; such stragglers ride along in the batch.
+
+Opt-in: ``MMRCA_GPU_JPEG=1`` together with ``--gpu_preprocess`` (``main_both.decode_only``).  ctypes prototypes come from the
+header through ``abi.prototypes``, as lib.py's are checked against mmrca.h."""
+from __future__ import annotations
+
+import ctypes as C
+import io
+import os
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from . import abi
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mmrca_jpeg.h")
+LIB_PATH = os.path.join(_HERE, "libmmrca_jpeg.so")
+HOST_FUNCTIONS = ("mmrca_jpeg_probe", "mmrca_jpeg_entropy_decode")
+DEVICE_FUNCTIONS = ("mmrca_jpeg_idct_rgb",)
+
+DESC_DTYPE = np.dtype([("out_offset", np.int64), ("coef_offset", np.int64), ("width", np.int32), ("height", np.int32), ("ncomp", np.int32),
+                       ("hmax", np.int32), ("vmax", np.int32), ("blk_off", np.int32, (3,)), ("bpr", np.int32, (3,)), ("bpc", np.int32, (3,)),
+                       ("reserved", np.int32, (2,)), ("qt", np.uint16, (192,))])
+assert DESC_DTYPE.itemsize == 464       # == sizeof(MmrcaJpegDesc)
+
+
+class JpegError(RuntimeError):
+    pass
+
+
+_header = None
+_host = None
+_device_fn = None
+
+
+def header() -> abi.Header:
+    global _header
+    if _header is None:
+        _header = abi.parse(HEADER_PATH)
+    return _header
+
+
+_enum_values = None
+
+
+def _constants() -> dict:
+    """every enumerator of the header: name -> value"""
+    global _enum_values
+    if _enum_values is None:
+        _enum_values = {name: value for e in header().enums for name, value in e.items()}
+    return _enum_values
+
+
+def _typed(lib, name):
+    restype, params = header().functions[name]
+    fn = getattr(lib, name)
+    fn.restype, fn.argtypes = restype, [t for t, _ in params]
+    return fn
+
+
+def load_host():
+    """libmmrca_jpeg.so with the header's prototypes (host code only: safe in DataLoader workers of any start method)"""
+    global _host
+    if _host is None:
+        if not os.path.exists(LIB_PATH):
+            raise JpegError(f"{LIB_PATH} not found: build it with __graft_entry__.build() (make -C garbage_classification_rca_amd/csrc)")
+        lib = C.CDLL(LIB_PATH)
+        for name in HOST_FUNCTIONS:
+            _typed(lib, name)
+        _host = lib
+    return _host
+
+
+def decline_reason(code: int) -> str:
+    for name, value in _constants().items():
+        if value == code and name.startswith("MMRCA_JPEG_") and not name.startswith("MMRCA_JPEG_INFO_"):
+            return name
+    return f"code {code}"
+
+
+def probe(data: bytes):
+    """(code, info): code 0 and the int32 record of mmrca_jpeg_probe (indices: the header's MMRCA_JPEG_INFO_* enumerators), or a
+    positive declined code and None"""
+    info = np.zeros(_constants()["MMRCA_JPEG_INFO_LEN"], dtype=np.int32)
+    data = bytes(data)
+    code = load_host().mmrca_jpeg_probe(data, len(data), info.ctypes.data)
+    return code, (info if code == 0 else None)
+
+
+def entropy_decode(data: bytes, return_code: bool = False):
+    """The coefficient record of one file, or None when the decoder declined it: {"info": int32 probe record, "coef": int16
+    coefficients (natural order, 64 per block, blocks in raster order per component, components back to back), "qt": uint16 [192]
+    quantisation table per component}.  return_code=True: (record or None, code)."""
+    data = bytes(data)
+    code, info = probe(data)
+    rec = None
+    if code == 0:
+        k = _constants()
+        n = int(info[k["MMRCA_JPEG_INFO_NCOEF"]])
+        coef = np.empty(n, dtype=np.int16)
+        qt = np.empty(192, dtype=np.uint16)
+        code = load_host().mmrca_jpeg_entropy_decode(data, len(data), coef.ctypes.data, n, qt.ctypes.data)
+        if code == 0:
+            rec = {"info": info, "coef": coef, "qt": qt}
+    return (rec, code) if return_code else rec
+
+
+def record_shape(rec) -> tuple:
+    """(height, width) of a coefficient record"""
+    k = _constants()
+    return int(rec["info"][k["MMRCA_JPEG_INFO_HEIGHT"]]), int(rec["info"][k["MMRCA_JPEG_INFO_WIDTH"]])
+
+
+def enabled() -> bool:
+    """the drivers' opt-in (with --gpu_preprocess): MMRCA_GPU_JPEG=1"""
+    return os.environ.get("MMRCA_GPU_JPEG", "") == "1"
+
+
+class JpegOrDecode:
+    """Dataset ``loader`` / ``transform`` pair in the place of (``pil_loader``, ``main_both.DecodeOnly``):
+
+        d = JpegOrDecode(); CustomImageTextFolder(root, loader=d.load, transform=d)
+
+    The worker reads the file once.  A baseline JPEG becomes its coefficient record; a declined file or a non-JPEG is decoded with
+    Pillow to the uint8 HWC tensor that DecodeOnly returns."""
+
+    def load(self, path: str):
+        with open(path, "rb") as f:
+            data = f.read()
+        rec = entropy_decode(data)
+        if rec is not None:
+            return rec
+        from PIL import Image
+        return Image.open(io.BytesIO(data)).convert("RGB")
+
+    def __call__(self, item):
+        if isinstance(item, dict):
+            return item
+        return torch.from_numpy(np.array(item.convert("RGB"), dtype=np.uint8))
+
+
+def pack_jpeg(items: Sequence) -> dict:
+    """Coefficient records and Pillow-decoded stragglers of one batch -> a handful of flat tensors (one shared-memory segment each
+    per batch, the rule preprocess.pack_images documents):
+        shapes [B, 2] int32 (h, w) in batch order; coef int16 (all records back to back); desc uint8 (one MmrcaJpegDesc per record,
+        out_offset = the image's place in the staging layout of the WHOLE batch); jpeg_index / straggler_index int64 (batch
+        positions); straggler_flat uint8 + straggler_shapes (pack_images of the stragglers)."""
+    from .preprocess import pack_images
+    k = _constants()
+    shapes = [record_shape(it) if isinstance(it, dict) else (int(it.shape[0]), int(it.shape[1])) for it in items]
+    offsets = np.concatenate([[0], np.cumsum([(h * w * 3 + 15) // 16 * 16 for h, w in shapes])]).astype(np.int64)
+    jpeg_index = [i for i, it in enumerate(items) if isinstance(it, dict)]
+    straggler_index = [i for i, it in enumerate(items) if not isinstance(it, dict)]
+    desc = np.zeros(len(jpeg_index), dtype=DESC_DTYPE)
+    coef = torch.empty(sum(items[i]["coef"].size for i in jpeg_index), dtype=torch.int16)
+    at = 0
+    for d, i in zip(desc, jpeg_index):
+        info, c = items[i]["info"], items[i]["coef"]
+        ncomp = int(info[k["MMRCA_JPEG_INFO_NCOMP"]])
+        bpr = info[k["MMRCA_JPEG_INFO_BPR"]:k["MMRCA_JPEG_INFO_BPR"] + 3]
+        bpc = info[k["MMRCA_JPEG_INFO_BPC"]:k["MMRCA_JPEG_INFO_BPC"] + 3]
+        d["out_offset"], d["coef_offset"] = offsets[i], at
+        d["width"], d["height"], d["ncomp"] = info[k["MMRCA_JPEG_INFO_WIDTH"]], info[k["MMRCA_JPEG_INFO_HEIGHT"]], ncomp
+        d["hmax"], d["vmax"] = info[k["MMRCA_JPEG_INFO_H"]], info[k["MMRCA_JPEG_INFO_V"]]
+        d["bpr"], d["bpc"] = bpr, bpc
+        d["blk_off"] = np.concatenate([[0], np.cumsum(bpr.astype(np.int64) * bpc)[:2]])
+        d["qt"] = items[i]["qt"]
+        coef[at:at + c.size] = torch.from_numpy(c)
+        at += c.size
+    stragglers = pack_images([items[i] for i in straggler_index]) if straggler_index else \
+        {"flat": torch.empty(0, dtype=torch.uint8), "shapes": torch.empty(0, 2, dtype=torch.int32)}
+    return {"shapes": torch.tensor(shapes, dtype=torch.int32).reshape(-1, 2), "coef": coef,
+            "desc": torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()),
+            "jpeg_index": torch.tensor(jpeg_index, dtype=torch.int64), "straggler_index": torch.tensor(straggler_index, dtype=torch.int64),
+            "straggler_flat": stragglers["flat"], "straggler_shapes": stragglers["shapes"]}
+
+
+def collate_jpeg(batch):
+    """``main_both.collate_decoded`` for JpegOrDecode items: default_collate, the images packed by ``pack_jpeg``"""
+    raws = [sample[0]["image"].pop("raw_image") for sample in batch]
+    data, labels = torch.utils.data.default_collate(batch)
+    data["image"]["raw_image"] = pack_jpeg(raws)
+    return data, labels
+
+
+def is_jpeg_batch(raw) -> bool:
+    return isinstance(raw, dict) and "coef" in raw and "desc" in raw
+
+
+def check_descriptors(desc: np.ndarray, n_coef: int, out_bytes: int) -> None:
+    """mmrca_jpeg_idct_rgb trusts its descriptors; this is the check against the buffer sizes that the header asks of the caller."""
+    if desc.size == 0:
+        return
+    bad = (desc["ncomp"] != 1) & (desc["ncomp"] != 3)
+    bad |= (desc["width"] < 1) | (desc["height"] < 1) | (desc["width"] > 16384) | (desc["height"] > 16384)
+    colour = desc["ncomp"] == 3
+    hv = desc["hmax"] * 10 + desc["vmax"]
+    bad |= np.where(colour, (hv != 11) & (hv != 21) & (hv != 22), hv != 11)
+    blocks = desc["bpr"].astype(np.int64) * desc["bpc"]
+    blocks[~colour, 1:] = 0
+    start = np.concatenate([np.zeros((len(desc), 1), dtype=np.int64), np.cumsum(blocks, axis=1)[:, :2]], axis=1)
+    bad |= np.where(colour, (desc["blk_off"] != start).any(axis=1), desc["blk_off"][:, 0] != 0)
+    w, h = desc["width"].astype(np.int64), desc["height"].astype(np.int64)
+    bad |= (desc["bpr"][:, 0] * 8 < w) | (desc["bpc"][:, 0] * 8 < h)
+    cw, ch = -(-w // desc["hmax"].clip(1)), -(-h // desc["vmax"].clip(1))
+    for c in (1, 2):
+        bad |= colour & ((desc["bpr"][:, c] * 8 < cw) | (desc["bpc"][:, c] * 8 < ch))
+    bad |= (desc["coef_offset"] < 0) | (desc["coef_offset"] % 64 != 0) | (desc["coef_offset"] + 64 * blocks.sum(axis=1) > n_coef)
+    bad |= (desc["out_offset"] < 0) | (desc["out_offset"] % 16 != 0) | (desc["out_offset"] + w * h * 3 > out_bytes)
+    if bad.any():
+        raise JpegError(f"jpeg batch: descriptor {int(np.flatnonzero(bad)[0])} does not fit its buffers (coef {n_coef} int16, out {out_bytes} B)")
+
+
+def idct_rgb(coef: torch.Tensor, desc: torch.Tensor, n_images: int, out: torch.Tensor) -> None:
+    """mmrca_jpeg_idct_rgb on the current stream: device tensors coef (int16, consumed), desc (uint8, n_images records that the caller
+    has checked with ``check_descriptors``) and out (uint8 staging layout)."""
+    global _device_fn
+    from . import lib as L
+    if _device_fn is None:
+        _device_fn = _typed(L.load(), "mmrca_jpeg_idct_rgb")
+    for t, dt, name in ((coef, torch.int16, "coef"), (desc, torch.uint8, "desc"), (out, torch.uint8, "out")):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise JpegError(f"idct_rgb: {name} must be a contiguous {dt} tensor in HBM")
+    if desc.numel() < n_images * DESC_DTYPE.itemsize:
+        raise JpegError("idct_rgb: fewer descriptors than images")
+    L._check(_device_fn(L.ptr(coef), L.ptr(desc), n_images, L.ptr(out), L.stream_ptr()), "mmrca_jpeg_idct_rgb")
+
+
+class GpuJpegDecoder:
+    """collate_jpeg's batch -> {"flat": uint8 on the device in the staging layout of pack_images, "shapes": [B, 2]} in batch order.
+
+    Coefficients, descriptors and straggler pixels go to the device on a copy stream, from the DataLoader's pinned tensors when it
+    pinned them; mmrca_jpeg_idct_rgb and the placement of the stragglers run on the caller's current stream.  Two slots alternate, so
+    batch i+1 can be copied while batch i is decoded; a returned ``flat`` stays valid, in the order of the caller's stream, until the
+    next call but one."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        self._copy_stream = torch.cuda.Stream(device=self.device)
+        self._coef = [torch.empty(0, dtype=torch.int16, device=self.device) for _ in range(2)]
+        self._desc = [torch.empty(0, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._strag = [torch.empty(0, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._out = [torch.empty(0, dtype=torch.uint8, device=self.device) for _ in range(2)]
+        self._free = [None, None]          # event: the launches that read this slot's coefficients have finished
+        self._keep = [None, None]          # the host tensors a slot's copies read from
+        self._i = 0
+
+    @staticmethod
+    def _fit(buf: torch.Tensor, n: int) -> torch.Tensor:
+        return buf if buf.numel() >= n else torch.empty(n + n // 4, dtype=buf.dtype, device=buf.device)
+
+    def __call__(self, batch: dict) -> dict:
+        shapes = batch["shapes"]
+        sizes = [(h * w * 3 + 15) // 16 * 16 for h, w in shapes.tolist()]
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(offsets[-1])
+        coef, desc, sflat = batch["coef"], batch["desc"], batch["straggler_flat"]
+        if coef.dtype != torch.int16 or desc.dtype != torch.uint8 or desc.numel() % DESC_DTYPE.itemsize:
+            raise JpegError("jpeg batch: coef must be int16 and desc whole MmrcaJpegDesc records")
+        n_jpeg = desc.numel() // DESC_DTYPE.itemsize
+        check_descriptors(desc.numpy().view(DESC_DTYPE), coef.numel(), total)
+        k = self._i & 1
+        self._i += 1
+        main = torch.cuda.current_stream(self.device)
+        if self._free[k] is not None:
+            self._copy_stream.wait_event(self._free[k])
+        with torch.cuda.device(self.device):
+            self._out[k] = self._fit(self._out[k], total)           # written on the caller's stream only
+        self._keep[k] = (coef, desc, sflat)
+        with torch.cuda.stream(self._copy_stream):                  # (a grown buffer is allocated in the stream that fills it)
+            self._coef[k], self._desc[k] = self._fit(self._coef[k], coef.numel()), self._fit(self._desc[k], desc.numel())
+            self._strag[k] = self._fit(self._strag[k], sflat.numel())
+            self._coef[k][:coef.numel()].copy_(coef, non_blocking=True)
+            self._desc[k][:desc.numel()].copy_(desc, non_blocking=True)
+            if sflat.numel():
+                self._strag[k][:sflat.numel()].copy_(sflat, non_blocking=True)
+        main.wait_stream(self._copy_stream)
+        out = self._out[k]
+        if n_jpeg:
+            idct_rgb(self._coef[k], self._desc[k], n_jpeg, out)
+        src = 0
+        for i, (h, w) in zip(batch["straggler_index"].tolist(), batch["straggler_shapes"].tolist()):
+            n = h * w * 3
+            if (h, w) != tuple(shapes[i].tolist()) or src + n > sflat.numel():
+                raise JpegError("jpeg batch: the stragglers do not match the batch's shapes")
+            out[int(offsets[i]):int(offsets[i]) + n].copy_(self._strag[k][src:src + n], non_blocking=True)
+            src += (n + 15) // 16 * 16
+        ev = torch.cuda.Event()
+        ev.record(main)
+        self._free[k] = ev
+        return {"flat": out[:total], "shapes": shapes}

@@ -33,14 +33,15 @@ class MmrcaError(RuntimeError):
 
 
 def build_library(force: bool = False) -> str:
-    """Compile every HIP source for gfx950 into libmmrca.so (hipcc cross-compiles without a GPU)."""
+    """Compile every HIP source for gfx950 into libmmrca.so (hipcc cross-compiles without a GPU); the same make builds the
+    host-only libmmrca_jpeg.so (csrc/jpeg_entropy.cpp, bound by jpeg.py)."""
     src_dir = os.path.join(_HERE, "csrc")
     cmd = ["make", "-C", src_dir, "-j8"]
     if force:
         subprocess.run(["make", "-C", src_dir, "clean"], check=True, capture_output=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0 or not os.path.exists(LIB_PATH):
-        raise MmrcaError("building libmmrca.so failed:\n" + r.stdout[-4000:] + r.stderr[-4000:])
+    if r.returncode != 0 or not os.path.exists(LIB_PATH) or not os.path.exists(os.path.join(_HERE, "libmmrca_jpeg.so")):
+        raise MmrcaError("building libmmrca.so / libmmrca_jpeg.so failed:\n" + r.stdout[-4000:] + r.stderr[-4000:])
     return LIB_PATH
 
 

@@ -89,6 +89,17 @@ def collate_decoded(batch):
     return data, labels
 
 
+def decode_only(root, **dataset_kw):
+    """(dataset, collate_fn) of the --gpu_preprocess input path.  Default: Pillow decodes in the workers (DecodeOnly,
+    collate_decoded).  MMRCA_GPU_JPEG=1: the workers only entropy-decode baseline JPEGs and the GPU does the rest (jpeg.JpegOrDecode,
+    jpeg.collate_jpeg; GpuImagePipeline takes either batch and returns the same tensors)."""
+    from . import jpeg
+    if jpeg.enabled():
+        decode = jpeg.JpegOrDecode()
+        return CustomImageTextFolder(root=root, loader=decode.load, transform=decode, **dataset_kw), jpeg.collate_jpeg
+    return CustomImageTextFolder(root=root, transform=DecodeOnly(), **dataset_kw), collate_decoded
+
+
 def get_class_weights(train_dataset_path):
     """main_both.py:61-78."""
     ds = CustomImageTextFolder(train_dataset_path)
@@ -186,7 +197,7 @@ def main(argv=None):
     _tokenizer = global_model.get_tokenizer()
     _max_len = args.tokens_max_len or global_model.get_max_token_size()
 
-    gpu_pre = False
+    gpu_pre, collate = False, None
     if args.synthetic:
         train_data = SyntheticImageTextDataset(args.synthetic, WIDTH, _max_len)
         val_data = SyntheticImageTextDataset(max(args.synthetic // 4, _batch_size), WIDTH, _max_len, seed_images=99, seed_text=77)
@@ -196,10 +207,14 @@ def main(argv=None):
         val_path = os.path.join(BASE_PATH, args.dataset_folder_name_val)
         class_weights = get_class_weights(train_path)
         gpu_pre = bool(args.gpu_preprocess)
-        train_data = CustomImageTextFolder(root=train_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT, True, args.prob_aug),
-                                           tokens_max_len=_max_len, tokenizer_text=_tokenizer, extended_desc=args.extended_desc_train)
-        val_data = CustomImageTextFolder(root=val_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT), tokens_max_len=_max_len,
-                                         tokenizer_text=_tokenizer, extended_desc=args.extended_desc_val)
+        text_kw = dict(tokens_max_len=_max_len, tokenizer_text=_tokenizer)
+        if gpu_pre:
+            train_data, collate = decode_only(train_path, extended_desc=args.extended_desc_train, **text_kw)
+            val_data, _ = decode_only(val_path, extended_desc=args.extended_desc_val, **text_kw)
+        else:
+            train_data = CustomImageTextFolder(root=train_path, transform=Transforms(WIDTH, HEIGHT, True, args.prob_aug),
+                                               extended_desc=args.extended_desc_train, **text_kw)
+            val_data = CustomImageTextFolder(root=val_path, transform=Transforms(WIDTH, HEIGHT), extended_desc=args.extended_desc_val, **text_kw)
     print("Class weights: {}".format(class_weights))
 
     # one shuffle seed for all ranks (random when --seed is not given, like the reference's unseeded loader); dropout streams
@@ -235,7 +250,7 @@ def main(argv=None):
         nw = D.loader_workers(args.num_workers)        # (capped by this rank's CPU slice, distributed.bind_rank_to_cpus)
         ctx = "forkserver" if (gpu_pre and nw > 0) else None
         return torch.utils.data.DataLoader(ds, batch_size=bs, sampler=sampler, num_workers=nw, pin_memory=True,
-                                           collate_fn=collate_decoded if gpu_pre else None, multiprocessing_context=ctx,
+                                           collate_fn=collate, multiprocessing_context=ctx,
                                            persistent_workers=bool(ctx)), sampler
 
     # The fine-tuning loaders are built when that phase starts, after the first phase's loaders are shut down: with persistent

@@ -205,6 +205,7 @@ class GpuImagePipeline:
         self._slot_free = [None, None]          # event: the kernel that consumed this slot has finished
         self._keep = [None, None]               # pinned batch a slot's H2D copy reads from (kept alive until the slot is reused)
         self._i = 0
+        self._jpeg = None                       # jpeg.GpuJpegDecoder, made when the first collate_jpeg batch arrives
         self._mean = (C.c_float * 3)(*(float(v) for v in mean))
         self._std = (C.c_float * 3)(*(float(v) for v in std))
         # One tiny batch through every stage NOW: loads the kernels' code objects and makes every device allocation before the
@@ -219,7 +220,14 @@ class GpuImagePipeline:
     def _stage(self, images, flips=None, aug=None, pad: bool = True):
         """The staging half of a call: take the next slot, write images and descriptors into its pinned buffers, start the
         H2D copies on the copy stream and order the caller's stream after them.  -> (slot, B, bytes of the rotate
-        descriptors, any rotation enabled); ``_release(slot)`` after the kernels that read the slot are launched."""
+        descriptors, any rotation enabled); ``_release(slot)`` after the kernels that read the slot are launched.
+        A packed batch whose ``flat`` already lives on this device (jpeg.GpuJpegDecoder's output) is copied into the slot on the
+        caller's stream instead, device to device; a ``jpeg.collate_jpeg`` batch is decoded first."""
+        if isinstance(images, dict) and "coef" in images:
+            from .jpeg import GpuJpegDecoder
+            if self._jpeg is None:
+                self._jpeg = GpuJpegDecoder(self.device)
+            images = self._jpeg(images)
         packed = images if isinstance(images, dict) else None           # pack_images() output: already in the staging layout
         shapes = [tuple(x) for x in packed["shapes"].tolist()] if packed is not None else [(int(im.shape[0]), int(im.shape[1])) for im in images]
         B = len(shapes)
@@ -260,7 +268,11 @@ class GpuImagePipeline:
             flat = packed["flat"]
             if flat.dtype != torch.uint8 or flat.numel() != off:
                 raise L.MmrcaError("GpuImagePipeline: packed batch does not match its shapes")
-            if flat.is_pinned():
+            if flat.is_cuda:
+                if flat.device != self._dev[k].device:
+                    raise L.MmrcaError(f"GpuImagePipeline: packed batch on {flat.device}, pipeline on {self.device}")
+                src = None                                  # decoded on the GPU: no host copy of the pixels exists
+            elif flat.is_pinned():
                 src = flat                                  # the DataLoader pinned it: copy to the device straight from there
                 self._keep[k] = flat
             else:
@@ -303,11 +315,14 @@ class GpuImagePipeline:
             ha[nr:nr + na] = augd.view(np.uint8).reshape(-1)
         main = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(self._copy_stream):
-            self._dev[k][:src_end].copy_(src[:src_end], non_blocking=True)
+            if src is not None:
+                self._dev[k][:src_end].copy_(src[:src_end], non_blocking=True)
             self._dev_desc[k][:nd].copy_(self._host_desc[k][:nd], non_blocking=True)
             if aug is not None:
                 self._dev_aug[k][:nr + na].copy_(self._host_aug[k][:nr + na], non_blocking=True)
         main.wait_stream(self._copy_stream)
+        if src is None:                                     # (the slot is free: _slot_free[k] was waited for above)
+            self._dev[k][:src_end].copy_(packed["flat"], non_blocking=True)
         return k, B, nr, any_rot
 
     def _release(self, k: int):

@@ -147,7 +147,7 @@ def train(kind, argv, build_model, batch_table):
     print("Class weights: {}".format(class_weights))
     image_pipeline, aug_params, collate = None, None, None
     if kind == "image":
-        from .main_both import DecodeOnly, Transforms, collate_decoded
+        from .main_both import Transforms, decode_only
         WIDTH, HEIGHT = global_model.get_image_size()
         gpu_pre = bool(args.gpu_preprocess)
         norm = {}           # A.Normalize constants for the train and validation pipelines; empty = ImageNet's
@@ -158,16 +158,16 @@ def train(kind, argv, build_model, batch_table):
             sums, batch_sizes = dataset_stats.compute(train_path, WIDTH, HEIGHT, device, pad=False, seed=args.seed, num_workers=args.num_workers)
             mean_train, std_train = dataset_stats.report(sums, batch_sizes, WIDTH * HEIGHT)
             norm = dict(mean=mean_train, std=std_train)
-        train_data = CustomImageTextFolder(root=train_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT, True, args.prob_aug, **norm))
-        val_data = CustomImageTextFolder(root=val_path, transform=DecodeOnly() if gpu_pre else Transforms(WIDTH, HEIGHT, **norm))
         if gpu_pre:
+            (train_data, collate), (val_data, _) = decode_only(train_path), decode_only(val_path)
             # the reference's TRAIN_PIPELINE / VALIDATION_PIPELINE (main_image.py:409-446) are main_both.py's lists
             from .preprocess import GpuImagePipeline, sample_train_params
             image_pipeline = GpuImagePipeline(HEIGHT, WIDTH, max_batch=max(_batch_size, _batch_size_FT), max_pixels=640 * 480, device=device, **norm)
             aug_rng = np.random.default_rng(None if args.seed is None else int(args.seed) + 7919)
             aug_params = lambda n: sample_train_params(aug_rng, n, args.prob_aug)      # noqa: E731
-            collate = collate_decoded
         else:
+            train_data = CustomImageTextFolder(root=train_path, transform=Transforms(WIDTH, HEIGHT, True, args.prob_aug, **norm))
+            val_data = CustomImageTextFolder(root=val_path, transform=Transforms(WIDTH, HEIGHT, **norm))
             print("CPU image transforms (--gpu_preprocess=false): of the training augmentations only the flips are applied")
     else:
         WIDTH = HEIGHT = 0
