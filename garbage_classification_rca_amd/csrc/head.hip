@@ -769,6 +769,7 @@ extern "C" int mmrca_head_bwd(const float* dlogits, const void* img, const void*
   MMRCA_REQUIRE(dlogits && w && g && img && txt, "head_bwd: null pointer");
   if (int rc = head_check(B, d_img, d_txt, n_classes, mode)) return rc;
   MMRCA_REQUIRE(head_weights_ok(w), "head_bwd: null weight pointer");
+  MMRCA_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "head_bwd: dropout p must be in [0,1)");
   {
     float* const* p = (float* const*)g;
     for (size_t i = 0; i < sizeof(MmrcaHeadGrads) / sizeof(float*); ++i) MMRCA_REQUIRE(p[i], "head_bwd: null gradient pointer");
