@@ -50,7 +50,7 @@ extern "C" int mmrca_mha_fwd_planes_in(const void* qkv_hi, const void* qkv_lo, c
   return mmrca_mha_fwd_f32m(qkv_hi, key_mask, out, lse, B, H, S, dh, scale, drop_p, drop_seed, cu_seqlens, (hipStream_t)stream, out_hi, out_lo, qkv_lo);
 }
 
-// The same arithmetic on the bf16 matrix cores: every product three-pass over the planes (attention_mfma.hip::mha_fwd_x3_k), S <= 224.
+// The same arithmetic on the bf16 matrix cores: every product three-pass over the planes (attention_mfma.hip::mha_fwd_x3_k; mha_fwd_x3_c_k for 225 <= S <= 512).
 // q|k|v AND the context as two bf16 planes; no fp32 tensor is read or written.  What the bf16x3f mode runs.
 int mmrca_mha_fwd_x3_launch(const void*, const void*, const int32_t*, void*, void*, float*, int, int, int, int, float, float, uint64_t, const int32_t*, hipStream_t);
 extern "C" int mmrca_mha_fwd_x3(const void* qkv_hi, const void* qkv_lo, const int32_t* key_mask, void* out_hi, void* out_lo, float* lse,

@@ -324,6 +324,148 @@ mha_fwd_x3_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ qkv_lo, 
 }
 
 // ------------------------------------------------------------------------------------------------------
+// bf16x3 forward over key CHUNKS (225 <= Smax <= 512: the text encoders at their full context in the bf16x3f mode)
+// ------------------------------------------------------------------------------------------------------
+// mha_fwd_x3_k keeps the four images of a whole head resident: 112 KiB at 14 key tiles, 256 KiB at S = 512 (a CU has 160).  Here the
+// images hold AT_CK = 128 keys at a time (64 KiB + the key bias: two workgroups fit on a CU, so one stages while the other computes)
+// and a workgroup of 8 waves owns 128 queries of one head, a wave 16 of them for the whole walk over the head's key chunks: its Q
+// fragments, its O accumulators and a running maximum / sum per query row stay in registers.  Per chunk the arithmetic is
+// mha_fwd_x3_k's (small terms first, P split in registers, exp2 domain); between chunks O and the sum are rescaled by
+// exp2(m_old - m_new).  A chunk without a live key for a row gives m_new == m_old: factor 1 (also when both are -inf), numerators 0,
+// so maximum, sum and O keep their bits -- which is why a packed run (only the live keys are walked: ceil(len / 128) chunks, and of
+// the last one only its live 32-key pairs are staged and multiplied) equals the padded run on every kept row.  Chunk boundaries are
+// the fixed key indices 128, 256, 384 in both layouts.  No atomics.
+#define AT_CK 128
+#define AT_CKT (AT_CK / 16)
+template <bool DROP>
+__global__ void __launch_bounds__(512, 4)
+mha_fwd_x3_c_k(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ qkv_lo, const int32_t* __restrict__ key_mask,
+               bf16_t* __restrict__ out_hi, bf16_t* __restrict__ out_lo, float* __restrict__ lse, int H, int Smax, float scale,
+               float drop_p, uint64_t drop_seed, const int32_t* __restrict__ cu, int nqg) {
+  const float drop_sc = DROP ? 1.f / (1.f - drop_p) : 1.f;
+  extern __shared__ __attribute__((aligned(16))) char sm[];
+  constexpr int IMG = AT_CK * 128;
+  char* Kh = sm; char* Kl = sm + IMG; char* Vh = sm + 2 * IMG; char* Vl = sm + 3 * IMG;
+  float* kb = reinterpret_cast<float*>(sm + 4 * IMG);           // the key bias of the WHOLE sequence: AT_MAX_S floats
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
+  const int bh = blockIdx.x / nqg, qg = blockIdx.x % nqg;
+  const int b = bh / H, h = bh % H;
+  AT_SEQ(b, Smax, cu)
+  if (qg * 128 >= S) return;                                    // (the whole workgroup: no barrier is left waiting)
+  const int64_t ld = 3LL * H * AT_DH;
+  const int64_t q_off = (int64_t)row0 * ld + h * AT_DH, k_off = q_off + H * AT_DH, v_off = k_off + H * AT_DH;
+  const int nch = (S + AT_CK - 1) / AT_CK;
+  stage_key_bias(kb, key_mask ? key_mask + row0 : nullptr, S, nch * AT_CK);
+  const float c1 = scale * LOG2E;                    // scores live in the exp2 domain
+  const int q0 = (qg * 8 + wave) * 16;
+  const bool has_tile = q0 < S;                      // wave-uniform
+  bf16x8 qh0, qh1, ql0, ql1;
+  if (has_tile) {
+    qh0 = frag_global(qkv + q_off, ld, q0, S, 0, lane); qh1 = frag_global(qkv + q_off, ld, q0, S, 1, lane);
+    ql0 = frag_global(qkv_lo + q_off, ld, q0, S, 0, lane); ql1 = frag_global(qkv_lo + q_off, ld, q0, S, 1, lane);
+  }
+  float mrun = -INFINITY, lrun = 0.f;
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int c = 0; c < nch; ++c) {
+    const int key0 = c * AT_CK;
+    const int nk = S - key0 < AT_CK ? S - key0 : AT_CK;         // live keys of this chunk, >= 1
+    const int nkp = (nk + 31) & ~31;                            // staged and multiplied: whole 32-key pairs
+    if (c) __syncthreads();                                     // every wave has left the previous chunk's images
+    stage_rows(Kh, IMG_ROW, qkv + k_off + key0 * ld, ld, nk, nkp);
+    stage_rows(Kl, IMG_ROW, qkv_lo + k_off + key0 * ld, ld, nk, nkp);
+    stage_rows(Vh, IMG_TR, qkv + v_off + key0 * ld, ld, nk, nkp);
+    stage_rows(Vl, IMG_TR, qkv_lo + v_off + key0 * ld, ld, nk, nkp);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (!has_tile) continue;
+    f32x4 s[AT_CKT];
+#pragma unroll
+    for (int kt = 0; kt < AT_CKT; ++kt) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      if (kt * 16 < nkp) {                                      // wave-uniform; rows past nkp were not staged
+        const bf16x8 kh0 = frag_rows(Kh, IMG_ROW, kt * 16, 0, lane), kh1 = frag_rows(Kh, IMG_ROW, kt * 16, 1, lane);
+        const bf16x8 kl0 = frag_rows(Kl, IMG_ROW, kt * 16, 0, lane), kl1 = frag_rows(Kl, IMG_ROW, kt * 16, 1, lane);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl0, qh0, a, 0, 0, 0);      // the small terms first
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl1, qh1, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh0, ql0, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh1, ql1, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh0, qh0, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh1, qh1, a, 0, 0, 0);
+      }
+      s[kt] = a;
+      if (kt & 1) __builtin_amdgcn_sched_barrier(0);
+    }
+    float mc = -INFINITY;
+#pragma unroll
+    for (int kt = 0; kt < AT_CKT; ++kt) {
+      const f32x4 bias = *reinterpret_cast<const f32x4*>(kb + key0 + kt * 16 + 4 * g);     // keys key0 + 16kt + 4g + r
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = fmaf(s[kt][r], c1, bias[r]);
+        s[kt][r] = v;
+        mc = fmaxf(mc, v);
+      }
+    }
+    const float mnew = fmaxf(mrun, colgroup_max(mc));
+    // rescale factor of what the earlier chunks left: 1 when the maximum did not move (also -inf -> -inf, where the difference
+    // would be NaN), 0 when this chunk holds the row's first live key
+    const float alpha = mnew == mrun ? 1.f : __builtin_amdgcn_exp2f(mrun - mnew);
+    const float msafe = mnew > -INFINITY ? mnew : 0.f;
+    float lc = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < AT_CKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float e = __builtin_amdgcn_exp2f(s[kt][r] - msafe); s[kt][r] = e; lc += e; }
+    lrun = lrun * alpha + colgroup_sum(lc);
+    mrun = mnew;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
+    if (DROP) {      // dropout acts on the normalised probabilities: mask the numerators, keep the denominator
+#pragma unroll
+      for (int kt = 0; kt < AT_CKT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[kt][r] *= attn_keep(drop_p, drop_sc, drop_seed, bh, Smax, q0 + l16, key0 + kt * 16 + 4 * g + r);
+    }
+#pragma unroll
+    for (int u = 0; u < AT_CKT / 2; ++u) {
+      if (u * 32 < nkp) {                                       // wave-uniform
+        const bf16x8 ph = pack_pair(s[2 * u], s[2 * u + 1]);
+        f32x4 ra, rb;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { ra[r] = s[2 * u][r] - (float)ph[r]; rb[r] = s[2 * u + 1][r] - (float)ph[4 + r]; }
+        const bf16x8 pl = pack_pair(ra, rb);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+          const bf16x8 vh = frag_cols_tr(Vh, u, dt, lane), vl = frag_cols_tr(Vl, u, dt, lane);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vl, ph, o[dt], 0, 0, 0);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, pl, o[dt], 0, 0, 0);
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, ph, o[dt], 0, 0, 0);   // O^T[d][q]
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  const int q = q0 + l16;
+  if (has_tile && q < S) {
+    const float inv = lrun > 0.f ? 1.f / lrun : 0.f;
+    const int64_t off = ((int64_t)row0 + q) * (H * AT_DH) + h * AT_DH;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      bf16x4 vh, vl;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const float v = o[dt][r] * inv; vh[r] = (bf16_t)v; vl[r] = (bf16_t)(v - (float)vh[r]); }
+      *reinterpret_cast<bf16x4*>(out_hi + off + dt * 16 + 4 * g) = vh;
+      *reinterpret_cast<bf16x4*>(out_lo + off + dt * 16 + 4 * g) = vl;
+    }
+    if (g == 0) lse[((int64_t)b * H + h) * Smax + q] = lrun > 0.f ? mrun * LN2 + __logf(lrun) : INFINITY;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // forward, persistent over heads (unmasked, no dropout, padded layout: the ViT's attention)
 // ------------------------------------------------------------------------------------------------------
 // The per-head kernel above spends half of its waves' lifetime parked: all waves of a (b,h) wait for the 50 KB K/V staging and
@@ -1580,12 +1722,28 @@ int mmrca_mha_fwd_mfma(const void* qkv, const int32_t* key_mask, void* out, floa
   return 0;
 }
 
-// bf16x3 attention forward (mha_fwd_x3_k): head dim 64, S <= 224
-bool mmrca_mha_x3_ok(int S, int dh) { return dh == AT_DH && S >= 1 && S <= 224; }
+// bf16x3 attention forward: head dim 64; S <= 224 on the resident-image kernels (mha_fwd_x3_p_k, mha_fwd_x3_k), 225 <= S <= 512 on the
+// chunked-key kernel (mha_fwd_x3_c_k)
+bool mmrca_mha_x3_ok(int S, int dh) { return dh == AT_DH && S >= 1 && S <= AT_MAX_S; }
 int mmrca_mha_fwd_x3_launch(const void* qkv_hi, const void* qkv_lo, const int32_t* key_mask, void* out_hi, void* out_lo, float* lse, int B, int H,
                             int S, int dh, float scale, float drop_p, uint64_t drop_seed, const int32_t* cu, hipStream_t st) {
-  MMRCA_REQUIRE(mmrca_mha_x3_ok(S, dh), "mha_fwd_x3: needs head dim 64 and 1 <= S <= 224 (got S=%d dh=%d)", S, dh);
+  MMRCA_REQUIRE(mmrca_mha_x3_ok(S, dh), "mha_fwd_x3: needs head dim 64 and 1 <= S <= 512 (got S=%d dh=%d)", S, dh);
   MMRCA_REQUIRE(((((uintptr_t)qkv_hi) | ((uintptr_t)qkv_lo)) & 15) == 0 && ((((uintptr_t)out_hi) | ((uintptr_t)out_lo)) & 7) == 0, "mha_fwd_x3: alignment");
+  if (S > 224) {      // key chunks of 128, 128 queries per workgroup
+    const int ldsb = 4 * AT_CK * 128 + AT_MAX_S * 4, nqg = (S + 127) / 128;
+    MMRCA_REQUIRE((int64_t)B * H * nqg <= 0x7fffffff, "mha_fwd_x3: grid too large");
+    if (drop_p > 0.f) {
+      MMRCA_MAX_LDS(ldsb, mha_fwd_x3_c_k<true>);
+      hipLaunchKernelGGL((mha_fwd_x3_c_k<true>), dim3(B * H * nqg), dim3(512), ldsb, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, key_mask,
+                         (bf16_t*)out_hi, (bf16_t*)out_lo, lse, H, S, scale, drop_p, drop_seed, cu, nqg);
+    } else {
+      MMRCA_MAX_LDS(ldsb, mha_fwd_x3_c_k<false>);
+      hipLaunchKernelGGL((mha_fwd_x3_c_k<false>), dim3(B * H * nqg), dim3(512), ldsb, st, (const bf16_t*)qkv_hi, (const bf16_t*)qkv_lo, key_mask,
+                         (bf16_t*)out_hi, (bf16_t*)out_lo, lse, H, S, scale, drop_p, drop_seed, cu, nqg);
+    }
+    MMRCA_CHECK_LAUNCH("mha_fwd_x3(chunked)");
+    return 0;
+  }
   const int nkt = pick_nkt(S);
   if (nkt == 14 && drop_p <= 0.f && !key_mask && !cu && S > 16 * 12) {     // the ViT's attention: 197 tokens, no mask
     const int ldsb = 4 * 14 * 16 * 128;

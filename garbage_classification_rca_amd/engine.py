@@ -595,8 +595,9 @@ class MMRCAEngine:
 
     def _qkv_planes_ok(self, S, dh):
         """bf16x3f: the q|k|v projection is written as two bf16 planes -- the fp32 attention forward rebuilds the fp32 values from
-        them and the bf16 attention backward reads the hi plane, so no fp32 copy and no cast pass exist"""
-        return self.x3f and self._ln_planes and self.attn_impl == L.IMPL_AUTO and L.mha_fwd_planes_ok(S, dh)
+        them (S <= 208) or multiplies them three-pass on the bf16 matrix cores (S <= 512), and the bf16 attention backward reads the hi
+        plane, so no fp32 copy and no cast pass exist"""
+        return self.x3f and self._ln_planes and self.attn_impl == L.IMPL_AUTO and (L.mha_fwd_planes_ok(S, dh) or L.mha_fwd_x3_ok(S, dh))
 
     def _mha_fwd(self, qkv, mask32, ctx, lse, B, H, S, dh, drop_p=0.0, drop_seed=0, cu=None):
         if isinstance(qkv, Planes):

@@ -442,7 +442,7 @@ def mha_fwd_planes_in(qkv_planes, key_mask, out, out_planes, lse, B, H, S, dh, s
 
 
 def mha_fwd_x3_ok(S, dh):
-    return dh == 64 and 1 <= S <= 224
+    return dh == 64 and 1 <= S <= 512
 
 
 def mha_fwd_x3(qkv_planes, key_mask, out_planes, lse, B, H, S, dh, scale, drop_p=0.0, drop_seed=0, cu=None):
