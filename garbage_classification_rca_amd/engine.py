@@ -594,18 +594,15 @@ class MMRCAEngine:
         return qkv16, self._hi(c, B if tail else rows, D)
 
     def _qkv_planes_ok(self, S, dh):
-        """bf16x3f: the q|k|v projection is written as two bf16 planes -- the fp32 attention forward rebuilds the fp32 values from
-        them (S <= 208) or multiplies them three-pass on the bf16 matrix cores (S <= 512), and the bf16 attention backward reads the hi
-        plane, so no fp32 copy and no cast pass exist"""
-        return self.x3f and self._ln_planes and self.attn_impl == L.IMPL_AUTO and (L.mha_fwd_planes_ok(S, dh) or L.mha_fwd_x3_ok(S, dh))
+        """bf16x3f: the q|k|v projection is written as two bf16 planes -- the attention forward multiplies them three-pass on the bf16
+        matrix cores (dh = 64, S <= 512; the fp32 pipe is 1/16 of their rate) and the bf16 attention backward reads the hi plane, so no
+        fp32 copy and no cast pass exist"""
+        return self.x3f and self._ln_planes and self.attn_impl == L.IMPL_AUTO and L.mha_fwd_x3_ok(S, dh)
 
     def _mha_fwd(self, qkv, mask32, ctx, lse, B, H, S, dh, drop_p=0.0, drop_seed=0, cu=None):
-        if isinstance(qkv, Planes):
+        if isinstance(qkv, Planes):         # (only where _qkv_planes_ok said so)
             key, pl = self._planes_of(ctx)
-            if L.mha_fwd_x3_ok(S, dh):      # three-pass products on the bf16 matrix cores (the fp32 pipe is 1/16 of their rate)
-                L.mha_fwd_x3((qkv.hi, qkv.lo), mask32, pl, lse, B, H, S, dh, dh ** -0.5, drop_p=drop_p, drop_seed=drop_seed, cu=cu)
-            else:
-                L.mha_fwd_planes_in((qkv.hi, qkv.lo), mask32, None, pl, lse, B, H, S, dh, dh ** -0.5, drop_p=drop_p, drop_seed=drop_seed, cu=cu)
+            L.mha_fwd_x3((qkv.hi, qkv.lo), mask32, pl, lse, B, H, S, dh, dh ** -0.5, drop_p=drop_p, drop_seed=drop_seed, cu=cu)
             self._plane_fresh.add(key)
             return
         if self.x3 and self._ln_planes and self.attn_impl == L.IMPL_AUTO and L.mha_fwd_planes_ok(S, dh):
@@ -629,9 +626,8 @@ class MMRCAEngine:
             bad = [n for n in taps if not 1 <= int(n) <= s.layers - 1]
             if bad:
                 raise L.MmrcaError(f"text taps {bad}: hidden_states indices must lie in [1, {s.layers - 1}] for {s.name}")
-        tap_rows = {}
         B, T = ids.shape
-        cap, D, Fd, H = B * T, s.dim, s.ffn, s.heads          # buffers are sized for the padded layout
+        cap, D, H = B * T, s.dim, s.heads          # buffers are sized for the padded layout
         dh = D // H
         ids32 = ids.to(torch.int32).contiguous().view(-1)
         if s.pos_offset:
@@ -658,59 +654,60 @@ class MMRCAEngine:
         mean0, rstd0 = stat("mean0"), stat("rstd0")
         dp = float(drop_p)
         sd = lambda layer, site: self._site_seed(drop_seed, layer, site)
-        post_attn_drop = dp if s.name != "distilbert" else 0.0     # BertSelfOutput drops the attention output, DistilBERT does not
         self._ln_fwd(emb, None, P + "embeddings.LayerNorm", None, x, mean0, rstd0, M, D, s.ln_eps, out_drop=(dp, sd(0, 0)), to_gemm=True)
-        layers = []
+        sv = dict(B=B, T=T, M=M, cu=cu, first=first, ids32=ids32, pos=pos, mask32=mask32, emb=emb, mean0=mean0, rstd0=rstd0, layers=[],
+                  drop_p=dp, drop_seed=drop_seed, taps={})
         for i in range(s.layers):
             K = S.text_layer_keys(s, i)
             last_tail = CLS_TAIL and i == s.layers - 1          # (the class-token attention reads fp32 q|k|v)
             qkv = self.planes_buf("t_qkv", cap, 3 * D, i if save else 0) if (self._qkv_planes_ok(T, dh) and not last_tail) else fb("qkv", 3 * D, i)
             ctx, lse = fb("ctx", D, i), self.vec("t_lse", _round_up(B * H * T, ROWPAD), torch.float32, i if save else 0)
             self._lin_fwd(x, P + K["q"] + ".weight", P + K["q"] + ".bias", qkv, M, 3 * D, D, wnumel=3 * D * D)
-            if CLS_TAIL and i == s.layers - 1:
+            if last_tail:
                 # class-token tail: the class-token query's attention, then rows b*T only (see CLS_TAIL above)
-                cb = lambda name, cols, dt=None: self.buf("t_" + name + "_c", B, cols, dt, i if save else 0)
-                ctx_c, x_c = cb("ctx", D), cb("xin", D)
+                ctx_c, x_c = (self.buf(name, B, D, None, i if save else 0) for name in ("t_ctx_c", "t_xin_c"))
                 lse = self.vec("t_lse_c", _round_up(B * H, ROWPAD), torch.float32, i if save else 0)
                 L.mha_cls_fwd(qkv, mask32, ctx_c, lse, B, H, T, dh, dh ** -0.5, self.dt, drop_p=dp, drop_seed=sd(i, 1), cu=cu)
                 x_c[:B].copy_(x.index_select(0, first))
-                att = cb("att", D)
-                self._lin_fwd(ctx_c, P + K["o"] + ".weight", P + K["o"] + ".bias", att, B, D, D)
-                s1, x1 = cb("s1", D), cb("x1", D)
-                m1, r1 = stat("m1c", i), stat("r1c", i)
-                self._ln_fwd(att, x_c, P + K["ln1"], s1, x1, m1, r1, B, D, s.ln_eps, in_drop=(post_attn_drop, sd(i, 2)), to_gemm=True)
-                h, g = cb("h", Fd, self._hdt), (self.planes_buf("t_g_c", B, Fd, i if save else 0) if self._g_planes else cb("g", Fd))
-                self._lin_fwd(x1, P + K["f1"] + ".weight", P + K["f1"] + ".bias", g, B, Fd, D, act=self._gelu_act, preact=h)
-                f = cb("f", D)
-                self._lin_fwd(g, P + K["f2"] + ".weight", P + K["f2"] + ".bias", f, B, D, Fd)
-                s2, xn = cb("s2", D), cb("xout", D)
-                m2, r2 = stat("m2c", i), stat("r2c", i)
-                self._ln_fwd(f, x1, P + K["ln2"], s2, xn, m2, r2, B, D, s.ln_eps, in_drop=(dp, sd(i, 3)))
-                layers.append(dict(x=x, qkv=qkv, ctx=ctx, lse=lse, s1=s1, x1=x1, m1=m1, r1=r1, h=h, g=g, s2=s2, m2=m2, r2=r2,
-                                   ctx_c=ctx_c, tail=True))
-                cls = xn[:B].clone()
-                return cls, dict(B=B, T=T, M=M, cu=cu, first=first, ids32=ids32, pos=pos, mask32=mask32, emb=emb, mean0=mean0, rstd0=rstd0, layers=layers,
-                                 drop_p=dp, drop_seed=drop_seed, taps=tap_rows)
+                xn, up = self._text_upper_forward(x_c, ctx_c, sv, i, K, B, B, "_c", save)
+                up.update(x=x, qkv=qkv, ctx=ctx, lse=lse, ctx_c=ctx_c, tail=True)
+                sv["layers"].append(up)
+                return xn[:B].clone(), sv
             self._mha_fwd(qkv, mask32, ctx, lse, B, H, T, dh, drop_p=dp, drop_seed=sd(i, 1), cu=cu)
-            att = fb("tmpD", D)
-            self._lin_fwd(ctx, P + K["o"] + ".weight", P + K["o"] + ".bias", att, M, D, D)
-            s1, x1 = fb("s1", D, i), fb("x1", D, i)
-            m1, r1 = stat("m1", i), stat("r1", i)
-            self._ln_fwd(att, x, P + K["ln1"], s1, x1, m1, r1, M, D, s.ln_eps, in_drop=(post_attn_drop, sd(i, 2)), to_gemm=True)
-            h, g = fb("h", Fd, i, self._hdt), (self.planes_buf("t_g", cap, Fd, i if save else 0) if self._g_planes else fb("g", Fd, i))
-            self._lin_fwd(x1, P + K["f1"] + ".weight", P + K["f1"] + ".bias", g, M, Fd, D, act=self._gelu_act, preact=h)   # fused mode: h <- gelu'(pre-activation)
-            f = fb("tmpD", D)
-            self._lin_fwd(g, P + K["f2"] + ".weight", P + K["f2"] + ".bias", f, M, D, Fd)
-            s2, xn = fb("s2", D, i), fb("x", D, i + 1)
-            m2, r2 = stat("m2", i), stat("r2", i)
-            self._ln_fwd(f, x1, P + K["ln2"], s2, xn, m2, r2, M, D, s.ln_eps, in_drop=(dp, sd(i, 3)), to_gemm=(i + 1 < s.layers))
-            layers.append(dict(x=x, qkv=qkv, ctx=ctx, lse=lse, s1=s1, x1=x1, m1=m1, r1=r1, h=h, g=g, s2=s2, m2=m2, r2=r2))
+            xn, up = self._text_upper_forward(x, ctx, sv, i, K, M, cap, "", save)
+            up.update(x=x, qkv=qkv, ctx=ctx, lse=lse)
+            sv["layers"].append(up)
             x = xn
             if taps and (i + 1) in taps:
-                tap_rows[i + 1] = x.index_select(0, first)
-        cls = x.index_select(0, first)
-        return cls, dict(B=B, T=T, M=M, cu=cu, first=first, ids32=ids32, pos=pos, mask32=mask32, emb=emb, mean0=mean0, rstd0=rstd0, layers=layers,
-                         drop_p=dp, drop_seed=drop_seed, taps=tap_rows)
+                sv["taps"][i + 1] = x.index_select(0, first)
+        return x.index_select(0, first), sv
+
+    def _text_upper_forward(self, x, ctx, sv, i, K, rows, cap, sfx, save):
+        """The half of text layer i's forward above the attention, the mirror image of ``_text_upper_backward``: out-projection -> LN1
+        -> FFN1 -> FFN2 -> LN2 on `rows` rows of the residual stream `x` and the context `ctx`, in buffers ``t_<name><sfx>`` of `cap`
+        rows (all rows: M, B*T, ""; class-token tail: B, B, "_c").  Returns (the layer's output, its entries of ``sv["layers"][i]``)."""
+        s, P = self.ts, "text_model."
+        D, Fd, tail = s.dim, s.ffn, bool(sfx)
+        lay, dp, seed = (i if save else 0), sv["drop_p"], sv["drop_seed"]
+        fb = lambda name, cols, l=lay, dt=None: self.buf("t_" + name + sfx, cap, cols, dt, l)
+        nstat, c = _round_up(sv["B"] * sv["T"], ROWPAD), ("c" if tail else "")       # (statistics: sized for all rows in both forms)
+        m1, r1, m2, r2 = [self.vec(n + c, nstat, torch.float32, lay) for n in ("t_m1", "t_r1", "t_m2", "t_r2")]
+        post_attn_drop = dp if s.name != "distilbert" else 0.0     # BertSelfOutput drops the attention output, DistilBERT does not
+        if tail:        # per layer, like everything else of the tail
+            att, f, xn = fb("att", D), fb("f", D), fb("xout", D)
+        else:           # the two branch outputs share one scratch, and the output is the next layer's input
+            att = f = fb("tmpD", D, 0)
+            xn = fb("x", D, i + 1 if save else 0)
+        self._lin_fwd(ctx, P + K["o"] + ".weight", P + K["o"] + ".bias", att, rows, D, D)
+        s1, x1, s2 = fb("s1", D), fb("x1", D), fb("s2", D)
+        self._ln_fwd(att, x, P + K["ln1"], s1, x1, m1, r1, rows, D, s.ln_eps, in_drop=(post_attn_drop, self._site_seed(seed, i, 2)), to_gemm=True)
+        h, g = fb("h", Fd, lay, self._hdt), (self.planes_buf("t_g" + sfx, cap, Fd, lay) if self._g_planes else fb("g", Fd))
+        self._lin_fwd(x1, P + K["f1"] + ".weight", P + K["f1"] + ".bias", g, rows, Fd, D, act=self._gelu_act, preact=h)   # fused mode: h <- gelu'(pre-activation)
+        self._lin_fwd(g, P + K["f2"] + ".weight", P + K["f2"] + ".bias", f, rows, D, Fd)
+        # (the top layer's output feeds no GEMM, on all rows or on the tail's)
+        self._ln_fwd(f, x1, P + K["ln2"], s2, xn, m2, r2, rows, D, s.ln_eps, in_drop=(dp, self._site_seed(seed, i, 3)),
+                     to_gemm=(not tail and i + 1 < s.layers))
+        return xn, dict(s1=s1, x1=x1, m1=m1, r1=r1, h=h, g=g, s2=s2, m2=m2, r2=r2)
 
     def _text_upper_backward(self, dy, sv, i, K, rows, cap, sfx):
         """The half of text layer i's backward above the attention: LN2 -> FFN2 -> FFN1 -> LN1 -> out-projection on `rows` rows, with
@@ -748,8 +745,7 @@ class MMRCAEngine:
         at the output of layer n - 1 before that layer's backward runs"""
         s, P = self.ts, "text_model."
         B, T = sv["B"], sv["T"]
-        M, D, H = sv["M"], s.dim, s.heads
-        dh, cu, first = D // H, sv["cu"], sv["first"]
+        M, D, first = sv["M"], s.dim, sv["first"]
         gb = lambda name, cols: self.buf("tg_" + name, B * T, cols, self.gdtype)
         dx = gb("dxA", D)
         tail = bool(sv["layers"][-1].get("tail"))
@@ -760,17 +756,11 @@ class MMRCAEngine:
             if tail and i == s.layers - 1:
                 self._text_backward_tail(dcls, sv, dx)
                 continue
-            K, a = S.text_layer_keys(s, i), sv["layers"][i]
+            K = S.text_layer_keys(s, i)
             if dtaps and (i + 1) in dtaps:
                 dx.index_add_(0, first, dtaps[i + 1].to(dx.dtype))
             ds1, dctx = self._text_upper_backward(dx, sv, i, K, M, B * T, "")
-            dqkv = gb("dqkv", 3 * D)
-            # the attention backward also reduces the q|k|v bias gradients (adjacent in the arena) while it has the tiles
-            qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "tg", B * T, B)
-            L.mha_bwd(qkv_b, sv["mask32"], ctx_b, dctx, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt, self.attn_impl,
-                      drop_p=sv["drop_p"], drop_seed=self._site_seed(sv["drop_seed"], i, 1), cu=cu)
-            self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1, wnumel=3 * D * D)
-            self._ready(f"text_layer_{i}")
+            self._text_lower_backward(dctx, ds1, dx, sv, i, K, False)
         ds0 = gb("ds2", D)
         self._ln_bwd(dx, sv["emb"], P + "embeddings.LayerNorm", sv["mean0"], sv["rstd0"], None, ds0, M, D,
                      dy_drop=(sv["drop_p"], self._site_seed(sv["drop_seed"], 0, 0)))
@@ -782,24 +772,33 @@ class MMRCAEngine:
 
     def _text_backward_tail(self, dcls, sv, dx):
         """Backward of the LAST text layer when its post-attention part ran on the class-token rows only (CLS_TAIL)."""
-        s, P = self.ts, "text_model."
-        B, T = sv["B"], sv["T"]
-        M, D, H = sv["M"], s.dim, s.heads
-        dh, i, cu, first = D // H, s.layers - 1, sv["cu"], sv["first"]
-        K, a = S.text_layer_keys(s, i), sv["layers"][i]
-        gb = lambda name, cols: self.buf("tg_" + name, B * T, cols, self.gdtype)
+        s = self.ts
+        B, T, M, D, i = sv["B"], sv["T"], sv["M"], s.dim, s.layers - 1
+        K = S.text_layer_keys(s, i)
         dxc = self.buf("tg_dx_c", B, D, self.gdtype)
         dxc[:B].copy_(dcls)
         ds1, dctx_c = self._text_upper_backward(dxc, sv, i, K, B, B, "_c")
         # back to all rows: the attention mixes the class-token gradient into every key / value row
-        ds1_full = gb("ds1", D)
+        ds1_full = self.buf("tg_ds1", B * T, D, self.gdtype)
         ds1_full[:M].zero_()
-        ds1_full.index_copy_(0, first, ds1[:B])
-        dqkv = gb("dqkv", 3 * D)
+        ds1_full.index_copy_(0, sv["first"], ds1[:B])
+        self._text_lower_backward(dctx_c, ds1_full, dx, sv, i, K, True)
+
+    def _text_lower_backward(self, dctx, ds1, dx, sv, i, K, cls_only):
+        """The half of text layer i's backward below the attention, on all rows: attention backward (cls_only: of the class-token queries
+        alone, dctx [B, D]) -> in-projection backward, which adds ds1 and writes the gradient at the layer input into dx."""
+        s, P = self.ts, "text_model."
+        B, T, M, D, H = sv["B"], sv["T"], sv["M"], s.dim, s.heads
+        dh, a = D // H, sv["layers"][i]
+        dqkv = self.buf("tg_dqkv", B * T, 3 * D, self.gdtype)
         qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "tg", B * T, B)
-        L.mha_cls_bwd(qkv_b, sv["mask32"], ctx_b, dctx_c, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt,
-                      drop_p=sv["drop_p"], drop_seed=self._site_seed(sv["drop_seed"], i, 1), cu=cu)
-        self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1_full, wnumel=3 * D * D)
+        dp, seed, cu = sv["drop_p"], self._site_seed(sv["drop_seed"], i, 1), sv["cu"]
+        if cls_only:
+            L.mha_cls_bwd(qkv_b, sv["mask32"], ctx_b, dctx, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt, drop_p=dp, drop_seed=seed, cu=cu)
+        else:
+            L.mha_bwd(qkv_b, sv["mask32"], ctx_b, dctx, a["lse"], dqkv, B, H, T, dh, dh ** -0.5, self.bdt, self.attn_impl, drop_p=dp, drop_seed=seed,
+                      cu=cu)
+        self._lin_bwd(dqkv, a["x"], P + K["q"] + ".weight", P + K["q"] + ".bias", dx, M, 3 * D, D, addend=ds1, wnumel=3 * D * D)
         self._ready(f"text_layer_{i}")
 
     # ------------------------------------------------------------------ vision encoder
@@ -808,7 +807,7 @@ class MMRCAEngine:
         B = images.shape[0]
         if tuple(images.shape[1:]) != (3, s.image, s.image):
             raise ValueError(f"images must be [B,3,{s.image},{s.image}], got {tuple(images.shape)}")
-        nP, Tn, D, Fd, H = s.tokens - 1, s.tokens, s.dim, s.ffn, s.heads
+        nP, Tn, D, H = s.tokens - 1, s.tokens, s.dim, s.heads
         dh, M, Kp = D // H, B * Tn, 3 * s.patch * s.patch
         fb = lambda name, rows, cols, l=0, dt=None: self.buf("v_" + name, rows, cols, dt, l if save else 0)
         stat = lambda name, l=0: self.vec("v_" + name, _round_up(M, ROWPAD), torch.float32, l if save else 0)
@@ -819,7 +818,7 @@ class MMRCAEngine:
         self._lin_fwd(patches, P + "conv_proj.weight", P + "conv_proj.bias", proj, B * nP, D, Kp, wnumel=D * Kp)
         x = fb("x", M, D, 0)
         L.vit_assemble_fwd(proj, self.W(P + "class_token"), self.W(P + "encoder.pos_embedding"), x, B, nP, D, self.dt)
-        layers = []
+        layers, feat, mf, rf = [], self.buf("v_feat", B, D), stat("mf"), stat("rf")
         # ViT residual adds ride on the NEXT LayerNorm (add_layernorm: s = x + res, y = LN(s)) instead of the GEMM epilogue: the
         # out-projection and FFN2 forward GEMMs become bias-only and qualify for the persistent 256x256 kernel (1,050-1,150 TFLOP/s
         # against 780 for the 128x128 kernel with its addend read); the LayerNorm reads one more operand and writes the sum.
@@ -839,56 +838,54 @@ class MMRCAEngine:
             ctx = fb("ctx", M, D, i)
             lse = self.vec("v_lse", _round_up(B * H * Tn, ROWPAD), torch.float32, i if save else 0)
             self._lin_fwd(y1, Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", qkv, M, 3 * D, D)
-            if CLS_TAIL and i == s.layers - 1:
-                # class-token tail: the class-token query's attention, then rows b*Tn only (see CLS_TAIL above)
-                cb = lambda name, cols, dt=None: fb(name + "_c", B, cols, i, dt)
-                ctx_c, x_c = cb("ctx", D), cb("xin", D)
+            if last_tail:
+                # class-token tail: the class-token query's attention, then rows b*Tn only (see CLS_TAIL above), with the residual
+                # adds in the GEMM epilogues (no 256-wide kernel to qualify for on B rows)
+                ctx_c, x_c = fb("ctx_c", B, D, i), fb("xin_c", B, D, i)
                 lse = self.vec("v_lse_c", _round_up(B * H, ROWPAD), torch.float32, i if save else 0)
                 L.mha_cls_fwd(qkv, None, ctx_c, lse, B, H, Tn, dh, dh ** -0.5, self.dt)
                 x_c[:B].copy_(x[:M].view(B, Tn, D)[:, 0])
-                x1 = cb("x1", D)
-                self._lin_fwd(ctx_c, Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", x1, B, D, D, addend=x_c)
-                y2, m2, r2 = (self.planes_buf("v_y2_c", B, D, i if save else 0) if self._ln_planes else cb("y2", D)), stat("m2c", i), stat("r2c", i)
-                self._ln_fwd(x1, None, Lk + "ln_2", None, y2, m2, r2, B, D, s.ln_eps)
-                h, g = cb("h", Fd, self._hdt), (self.planes_buf("v_g_c", B, Fd, i if save else 0) if self._g_planes else cb("g", Fd))
-                self._lin_fwd(y2, Lk + "mlp.0.weight", Lk + "mlp.0.bias", g, B, Fd, D, act=self._gelu_act, preact=h)
-                xn = cb("xout", D)
-                self._lin_fwd(g, Lk + "mlp.3.weight", Lk + "mlp.3.bias", xn, B, D, Fd, addend=x1)
-                layers.append(dict(x=x, y1=y1, m1=m1, r1=r1, qkv=qkv, ctx=ctx, lse=lse, x1=x1, y2=y2, m2=m2, r2=r2, h=h, g=g,
-                                   ctx_c=ctx_c, tail=True))
-                feat = self.buf("v_feat", B, D)
-                mf, rf = stat("mf"), stat("rf")
+                xn, _, up = self._vision_upper_forward(x_c, ctx_c, i, B, "_c", save, False)
+                up.update(x=x, y1=y1, m1=m1, r1=r1, qkv=qkv, ctx=ctx, lse=lse, ctx_c=ctx_c, tail=True)
+                layers.append(up)
                 self._ln_fwd(xn, None, P + "encoder.ln", None, feat, mf, rf, B, D, s.ln_eps)
                 return feat[:B], dict(B=B, patches=patches, xL=xn, mf=mf, rf=rf, layers=layers)
             self._mha_fwd(qkv, None, ctx, lse, B, H, Tn, dh)
-            x1 = fb("x1", M, D, i)
-            y2, m2, r2 = (self.planes_buf("v_y2", M, D, i if save else 0) if self._ln_planes else fb("y2", M, D, i)), stat("m2", i), stat("r2", i)
-            if fuse_res:
-                ao = fb("attn_o", M, D, 0)
-                self._lin_fwd(ctx, Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", ao, M, D, D)
-                self._ln_fwd(ao, x, Lk + "ln_2", x1, y2, m2, r2, M, D, s.ln_eps)                 # x1 = attention output + x, y2 = LN(x1)
-            else:
-                self._lin_fwd(ctx, Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", x1, M, D, D, addend=x)
-                self._ln_fwd(x1, None, Lk + "ln_2", None, y2, m2, r2, M, D, s.ln_eps)
-            h, g = fb("h", M, Fd, i, self._hdt), (self.planes_buf("v_g", M, Fd, i if save else 0) if self._g_planes else fb("g", M, Fd, i))
-            self._lin_fwd(y2, Lk + "mlp.0.weight", Lk + "mlp.0.bias", g, M, Fd, D, act=self._gelu_act, preact=h)   # fused mode: h <- gelu'(pre-activation)
-            layers.append(dict(x=x, y1=y1, m1=m1, r1=r1, qkv=qkv, ctx=ctx, lse=lse, x1=x1, y2=y2, m2=m2, r2=r2, h=h, g=g))
-            if fuse_res:
-                f2 = fb("ffn_o", M, D, 0)
-                self._lin_fwd(g, Lk + "mlp.3.weight", Lk + "mlp.3.bias", f2, M, D, Fd)
-                pend = (f2, x1)
-            else:
-                xn = fb("x", M, D, i + 1)
-                self._lin_fwd(g, Lk + "mlp.3.weight", Lk + "mlp.3.bias", xn, M, D, Fd, addend=x1)
+            xn, pend, up = self._vision_upper_forward(x, ctx, i, M, "", save, fuse_res)
+            up.update(x=x, y1=y1, m1=m1, r1=r1, qkv=qkv, ctx=ctx, lse=lse)
+            layers.append(up)
+            if not fuse_res:
                 x = xn
-        feat = self.buf("v_feat", B, D)
-        mf, rf = stat("mf"), stat("rf")
         if pend is None:
             self._ln_fwd(x, None, P + "encoder.ln", None, feat, mf, rf, B, D, s.ln_eps, ld_x=Tn * D, ld_y=D)
         else:               # class-token rows only: x = ffn2 + x1 of the top layer at rows b*Tn
             x = fb("x", M, D, s.layers)
             self._ln_fwd(pend[0], pend[1], P + "encoder.ln", x, feat, mf, rf, B, D, s.ln_eps, ld_x=Tn * D, ld_y=D)
         return feat[:B], dict(B=B, patches=patches, xL=x, mf=mf, rf=rf, layers=layers)
+
+    def _vision_upper_forward(self, x, ctx, i, rows, sfx, save, fuse_res):
+        """The half of ViT layer i's forward above the attention, the mirror image of ``_vision_upper_backward``: out-projection -> LN2 ->
+        FFN1 -> FFN2 on `rows` rows of the residual stream `x` and the context `ctx` (all rows: B*Tn, buffers ``v_<name>``; class-token
+        tail: B, ``v_<name>_c``).  fuse_res: the residual adds ride on the LayerNorm that follows instead of the GEMM epilogues (see
+        ``_vision_forward``), so FFN2's output comes back without its residual as pend = (ffn2 output, x1) where the other form returns
+        the layer's output xn.  Returns (xn, pend, this half's entries of the saved layer)."""
+        s = self.vs
+        D, Fd = s.dim, s.ffn
+        Lk = f"image_model.encoder.layers.encoder_layer_{i}."
+        lay, c, nstat = (i if save else 0), ("c" if sfx else ""), _round_up(rows * s.tokens if sfx else rows, ROWPAD)     # (statistics: sized for all B*Tn rows in both forms)
+        fb = lambda name, cols, l=lay, dt=None: self.buf("v_" + name + sfx, rows, cols, dt, l)
+        x1 = fb("x1", D)
+        y2 = self.planes_buf("v_y2" + sfx, rows, D, lay) if self._ln_planes else fb("y2", D)
+        m2, r2 = self.vec("v_m2" + c, nstat, torch.float32, lay), self.vec("v_r2" + c, nstat, torch.float32, lay)
+        ao = fb("attn_o", D, 0) if fuse_res else x1
+        self._lin_fwd(ctx, Lk + "self_attention.out_proj.weight", Lk + "self_attention.out_proj.bias", ao, rows, D, D, addend=(None if fuse_res else x))
+        # fuse_res: x1 = attention output + x is formed here; y2 = LN(x1) either way
+        self._ln_fwd(ao, (x if fuse_res else None), Lk + "ln_2", (x1 if fuse_res else None), y2, m2, r2, rows, D, s.ln_eps)
+        h, g = fb("h", Fd, lay, self._hdt), (self.planes_buf("v_g" + sfx, rows, Fd, lay) if self._g_planes else fb("g", Fd))
+        self._lin_fwd(y2, Lk + "mlp.0.weight", Lk + "mlp.0.bias", g, rows, Fd, D, act=self._gelu_act, preact=h)    # fused mode: h <- gelu'(pre-activation)
+        out = fb("ffn_o", D, 0) if fuse_res else (fb("xout", D) if sfx else fb("x", D, i + 1 if save else 0))
+        self._lin_fwd(g, Lk + "mlp.3.weight", Lk + "mlp.3.bias", out, rows, D, Fd, addend=(None if fuse_res else x1))
+        return (None if fuse_res else out), ((out, x1) if fuse_res else None), dict(x1=x1, y2=y2, m2=m2, r2=r2, h=h, g=g)
 
     def _vision_upper_backward(self, dx, sv, i, rows, sfx):
         """The half of ViT layer i's backward above the attention: FFN2 -> FFN1 -> LN2 -> out-projection on `rows` rows (all rows:
@@ -913,8 +910,8 @@ class MMRCAEngine:
     def _vision_backward(self, dfeat, sv):
         s, P = self.vs, "image_model."
         B = sv["B"]
-        nP, Tn, D, H = s.tokens - 1, s.tokens, s.dim, s.heads
-        dh, M, Kp = D // H, B * Tn, 3 * s.patch * s.patch
+        nP, Tn, D = s.tokens - 1, s.tokens, s.dim
+        M, Kp = B * Tn, 3 * s.patch * s.patch
         gb = lambda name, rows, cols: self.buf("vg_" + name, rows, cols, self.gdtype)
         dx = gb("dxA", M, D)
         dfe = gb("dfeat", B, D)
@@ -934,16 +931,8 @@ class MMRCAEngine:
             if tail and i == s.layers - 1:
                 self._vision_backward_tail(dxc, sv, dx)
                 continue
-            Lk, a = P + f"encoder.layers.encoder_layer_{i}.", sv["layers"][i]
             dctx, dx1 = self._vision_upper_backward(dx, sv, i, M, "")
-            dqkv = gb("dqkv", M, 3 * D)
-            qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "vg", M, B)
-            L.mha_bwd(qkv_b, None, ctx_b, dctx, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt, self.attn_impl)
-            dy1 = gb("dy", M, D)
-            self._lin_bwd(dqkv, a["y1"], Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", dy1, M, 3 * D, D)
-            below = P + f"encoder.layers.encoder_layer_{i - 1}.mlp.3.bias"
-            self._ln_bwd(dy1, a["x"], Lk + "ln_1", a["m1"], a["r1"], dx1, dx, M, D, dcol=(self.G(below) if i > 0 else None))
-            self._ready(f"image_layer_{i}")
+            self._vision_lower_backward(dctx, dx1, dx, sv, i, False)
         dproj = gb("dproj", B * nP, D)
         L.vit_assemble_bwd(dx, dproj, self.Gflat(P + "class_token", D), self.Gflat(P + "encoder.pos_embedding", Tn * D), B, nP, D, self.bdt)
         self._lin_bwd(dproj, sv["patches"], P + "conv_proj.weight", P + "conv_proj.bias", None, B * nP, D, Kp, wnumel=D * Kp)
@@ -952,22 +941,30 @@ class MMRCAEngine:
     def _vision_backward_tail(self, dxc, sv, dx):
         """Backward of the LAST ViT layer when its post-attention part ran on the class-token rows only (CLS_TAIL);
         dxc [B, D] is the gradient at the layer's class-token output, dx [B*Tn, D] receives the gradient at its input."""
-        s, P = self.vs, "image_model."
-        B = sv["B"]
-        Tn, D, H = s.tokens, s.dim, s.heads
-        dh, M, i = D // H, B * Tn, s.layers - 1
-        Lk, a = P + f"encoder.layers.encoder_layer_{i}.", sv["layers"][i]
-        gb = lambda name, rows, cols: self.buf("vg_" + name, rows, cols, self.gdtype)
+        s = self.vs
+        B, Tn, D, i = sv["B"], s.tokens, s.dim, s.layers - 1
+        M = B * Tn
         dctx_c, dx1c = self._vision_upper_backward(dxc, sv, i, B, "_c")
         # back to all rows: the attention mixes the class-token gradient into every key / value row, and the residual
         # stream carries it straight down at the class-token rows
-        dx1 = gb("dxB", M, D)
+        dx1 = self.buf("vg_dxB", M, D, self.gdtype)
         dx1[:M].zero_()
         dx1[:M].view(B, Tn, D)[:, 0] = dx1c[:B]
-        dqkv = gb("dqkv", M, 3 * D)
+        self._vision_lower_backward(dctx_c, dx1, dx, sv, i, True)
+
+    def _vision_lower_backward(self, dctx, dx1, dx, sv, i, cls_only):
+        """The half of ViT layer i's backward below the attention, on all rows: attention backward (cls_only: of the class-token queries
+        alone, dctx [B, D]) -> in-projection backward -> LN1 backward, which adds dx1 and writes the gradient at the layer input into dx."""
+        s, P = self.vs, "image_model."
+        B, Tn, D, H = sv["B"], s.tokens, s.dim, s.heads
+        dh, M = D // H, B * Tn
+        Lk, a = P + f"encoder.layers.encoder_layer_{i}.", sv["layers"][i]
+        dqkv, dy1 = self.buf("vg_dqkv", M, 3 * D, self.gdtype), self.buf("vg_dy", M, D, self.gdtype)
         qkv_b, ctx_b = self._attn_bwd_operands(a, M, D, "vg", M, B)
-        L.mha_cls_bwd(qkv_b, None, ctx_b, dctx_c, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt)
-        dy1 = gb("dy", M, D)
+        if cls_only:
+            L.mha_cls_bwd(qkv_b, None, ctx_b, dctx, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt)
+        else:
+            L.mha_bwd(qkv_b, None, ctx_b, dctx, a["lse"], dqkv, B, H, Tn, dh, dh ** -0.5, self.bdt, self.attn_impl)
         self._lin_bwd(dqkv, a["y1"], Lk + "self_attention.in_proj_weight", Lk + "self_attention.in_proj_bias", dy1, M, 3 * D, D)
         below = P + f"encoder.layers.encoder_layer_{i - 1}.mlp.3.bias"
         self._ln_bwd(dy1, a["x"], Lk + "ln_1", a["m1"], a["r1"], dx1, dx, M, D, dcol=(self.G(below) if i > 0 else None))

@@ -33,17 +33,12 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 
 from . import lib as L
-
-ROWPAD = 256
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
+from .engine import ROWPAD, Planes, _round_up, parse_dtype
 
 
 @dataclass(frozen=True)
@@ -147,23 +142,27 @@ class _FrozenStore:
         return self.w[off:off + numel]
 
 
+class _Hidden(NamedTuple):
+    """The Q-Former's hidden state, a LayerNorm output that is also the next residual: ``res`` is what the next add reads, ``op`` what
+    the next GEMM reads -- the same tensor, or in the bf16x3f mode the plane pair the LayerNorm writes next to the fp32 copy (the one
+    place where it writes both: the two swap together)."""
+    res: torch.Tensor
+    op: Union[torch.Tensor, Planes]
+
+
 class Blip2QFormerEngine:
     """Frozen ViT-g + Q-Former forward and the trainable 4-class classifier of one replica on one GPU."""
 
     def __init__(self, spec: Blip2Spec = BLIP2_OPT_2_7B, dtype=torch.bfloat16, device="cuda",
                  gemm_impl: int = L.IMPL_AUTO, attn_impl: int = L.IMPL_AUTO):
         """dtype: torch.bfloat16 (fastest; logits ~2e-2 from the reference's fp32 arithmetic at full depth) | torch.float32 (fp32
-        matrix cores / VALU attention: the parity mode) | "bf16x3f" (= "bf16x3" here, the towers are frozen and forward-only): fp32
+        matrix cores / VALU attention: the parity mode) | "bf16x3f" (= "bf16x3" here, the towers are frozen and forward-only; every spelling
+        ``engine.parse_dtype`` accepts): fp32
         residual stream, LayerNorm and softmax statistics, every nn.Linear AND both attention products as three-pass split-bf16
         products on the bf16 matrix cores -- the fp32 arithmetic to ~1e-5 on the logits at a third of the bf16 MFMA rate: the fast
         mode inside the 1e-3 tolerance."""
         L.load()
-        name = dtype.lower() if isinstance(dtype, str) else ""
-        self.x3 = name in ("bf16x3f", "bf16x3")
-        if self.x3:
-            dtype = torch.float32
-        elif isinstance(dtype, str):
-            dtype = {"bf16": torch.bfloat16, "fp32": torch.float32, "f32": torch.float32}[name]
+        dtype, self.x3, _ = parse_dtype(dtype)
         self.mode = "bf16x3f" if self.x3 else ("bf16" if dtype == torch.bfloat16 else "fp32")
         self.s, self.dtype, self.device = spec, dtype, torch.device(device)
         self.dt = L.dtype_code(dtype)
@@ -280,37 +279,57 @@ class Blip2QFormerEngine:
         self._bufs.clear()
         self._x_cls = None
 
+    # An activation is one tensor in the compute dtype or, in the bf16x3f mode, a pair of bf16 planes (engine.Planes) where only GEMMs
+    # read it: LayerNorm outputs, attention context, MLP hidden, image_embeds.  q|k|v and the fused K|V stay fp32 tensors there (the
+    # attention splits them while staging), and so does the residual stream.  The three helpers below take and produce either form, so
+    # the two loops of the forward are written once.
+    def act(self, name, rows, cols) -> Union[torch.Tensor, Planes]:
+        """the buffer of an activation only GEMMs read"""
+        if self.x3:
+            return Planes(self.buf(name + ".hi", rows, cols, torch.bfloat16), self.buf(name + ".lo", rows, cols, torch.bfloat16))
+        return self.buf(name, rows, cols)
+
+    def hidden(self, name, rows, cols) -> "_Hidden":
+        y = self.buf(name, rows, cols)
+        return _Hidden(y, self.act(name + "p", rows, cols) if self.x3 else y)
+
+    def _tile_rows(self, M: int) -> int:
+        """Row count of a GEMM over a whole (zero-padded) activation buffer: whole 256-row tiles, which is what lets the dispatcher give
+        the persistent 256x256 kernels the shapes they take (N % 256 == 0: FFN1 and the Q-Former's K|V projection) -- in bf16 and in
+        every three-pass product; the fp32 kernel has no such form and gets M.  Rows >= M are never read by the attention or the
+        LayerNorms."""
+        return _round_up(M, ROWPAD) if (self.x3 or self.dtype == torch.bfloat16) else M
+
     def _lin(self, x, wkey, bkey, out, M, N, K, act=L.ACT_NONE, addend=None, wnumel=None):
-        w = self.store.view(wkey) if wnumel is None else self.store.flat(wkey, wnumel)
+        """nn.Linear.  x as a plane pair: the three-pass product on the planes of the weight (out: an fp32 tensor, or a plane pair when
+        only other such products read it; bias / addend fp32).  It picks its own kernel, whatever ``gemm_impl`` says: that argument
+        selects among the single-pass kernels."""
         b = self.store.view(bkey) if wnumel is None else self.store.flat(bkey, N)
+        if isinstance(x, Planes):
+            off, _, n = self.store.offsets[wkey]
+            n = n if wnumel is None else wnumel
+            po = isinstance(out, Planes)
+            L.gemm_x3((x.hi, x.lo), (self.w_hi[off:off + n], self.w_lo[off:off + n]), out.hi if po else out, C_lo=(out.lo if po else None),
+                      bias=b, addend=addend, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, a_layout=L.ROWK, b_layout=L.ROWK, act=act, impl=L.IMPL_AUTO)
+            return
+        w = self.store.view(wkey) if wnumel is None else self.store.flat(wkey, wnumel)
         L.gemm(x, w, out, bias=b, addend=addend, M=M, N=N, K=K, lda=K, ldb=K, ldc=N, a_layout=L.ROWK, b_layout=L.ROWK, act=act,
                dtype=self.dt, impl=self.gemm_impl)
 
-    def pbuf(self, name, rows, cols):
-        """an fp32 [rows, cols] matrix as two bf16 planes (the operand form of the bf16x3 GEMMs)"""
-        return self.buf(name + ".hi", rows, cols, torch.bfloat16), self.buf(name + ".lo", rows, cols, torch.bfloat16)
-
-    def _lin3(self, xp, wkey, bkey, out, M, N, K, act=L.ACT_NONE, addend=None, wnumel=None):
-        """bf16x3 nn.Linear: xp = (hi, lo) planes of the fp32 input; out = an fp32 tensor, or a (hi, lo) pair when only other
-        bf16x3 GEMMs read it; bias / addend fp32"""
-        off = self.store.offsets[wkey][0]
-        n = self.store.offsets[wkey][2] if wnumel is None else wnumel
-        w = (self.w_hi[off:off + n], self.w_lo[off:off + n])
-        b = self.store.view(bkey) if wnumel is None else self.store.flat(bkey, N)
-        planes = isinstance(out, tuple)
-        L.gemm_x3(xp, w, out[0] if planes else out, C_lo=out[1] if planes else None, bias=b, addend=addend, M=M, N=N, K=K, lda=K, ldb=K,
-                  ldc=N, a_layout=L.ROWK, b_layout=L.ROWK, act=act, impl=L.IMPL_AUTO)
-
-    def _ln3(self, x, res, pfx, y, yp, rows, D, eps, in_drop=(0.0, 0), out_drop=(0.0, 0)):
-        """fp32 LayerNorm whose output leaves as two bf16 planes yp (and as fp32 in y when it is also the next residual)"""
+    def _ln(self, x, res, pfx, y, rows, D, eps, in_drop=(0.0, 0), out_drop=(0.0, 0)):
+        """y: a tensor, a plane pair (written as planes ONLY: the vision tower, nothing else reads it) or a ``_Hidden``"""
+        full, op = y if isinstance(y, _Hidden) else ((None, y) if isinstance(y, Planes) else (y, None))
         mean, rstd = self.buf("ln_mean", rows, 1, torch.float32), self.buf("ln_rstd", rows, 1, torch.float32)
-        L.add_layernorm_fwd(x, res, self.store.view(pfx + ".weight"), self.store.view(pfx + ".bias"), None, y, mean, rstd, rows, D,
-                            D, D, eps, L.F32, in_drop=in_drop, out_drop=out_drop, y_planes=yp)
+        L.add_layernorm_fwd(x, res, self.store.view(pfx + ".weight"), self.store.view(pfx + ".bias"), None, full, mean, rstd, rows, D,
+                            D, D, eps, self.dt, in_drop=in_drop, out_drop=out_drop, y_planes=((op.hi, op.lo) if isinstance(op, Planes) else None))
 
-    def _ln(self, x, res, pfx, y, rows, D, eps, in_drop=(0.0, 0), out_drop=(0.0, 0), sum_out=None):
-        mean, rstd = self.buf("ln_mean", rows, 1, torch.float32), self.buf("ln_rstd", rows, 1, torch.float32)
-        L.add_layernorm_fwd(x, res, self.store.view(pfx + ".weight"), self.store.view(pfx + ".bias"), sum_out, y, mean, rstd, rows, D,
-                            D, D, eps, self.dt, in_drop=in_drop, out_drop=out_drop)
+    def _attn(self, q, ldq, k, ldk, v, ldv, out, ldo, B, H, Sq, Skv, dh, drop_p=0.0, drop_seed=0):
+        """softmax(q k^T / sqrt(dh)) v over row-strided q / k / v tensors; a plane-pair `out` selects the three-pass kernel"""
+        if isinstance(out, Planes):
+            L.mha_cross_fwd_x3(q, ldq, k, ldk, v, ldv, (out.hi, out.lo), ldo, B, H, Sq, Skv, dh, dh ** -0.5, drop_p=drop_p, drop_seed=drop_seed)
+        else:
+            L.mha_cross_fwd(q, ldq, k, ldk, v, ldv, out, ldo, B, H, Sq, Skv, dh, dh ** -0.5, self.dt, self.attn_impl, drop_p=drop_p,
+                            drop_seed=drop_seed)
 
     @staticmethod
     def _site_seed(base: int, layer: int, site: int) -> int:
@@ -336,140 +355,68 @@ class Blip2QFormerEngine:
         L.vit_assemble_fwd(proj, self.store.view("vision_model.embeddings.class_embedding"),
                            self.store.view("vision_model.embeddings.position_embedding"), x, B, nP, D, self.dt)
         dh = D // s.v_heads
-        if self.x3:
-            return self._vision_layers_x3(x, B)
-        y, qkv, ao, x1 = self.buf("vy", M, D), self.buf("vqkv", M, 3 * D), self.buf("vao", M, D), self.buf("vx1", M, D)
-        h = self.buf("vh", M, s.v_mlp)
-        # GEMMs run over whole 256-row tiles of the (zero-padded) buffers: that is what lets the dispatcher give the
-        # persistent 256x256 kernel the shapes it takes (N % 256 == 0: FFN1 and the Q-Former's K|V projection); rows >= M
-        # are never read by the attention or the LayerNorms.  The residual adds ride on the GEMM epilogues (addend): moving
-        # them onto the next LayerNorm, as the ViT-B encoder in engine.py does, measured slower here (N = 1408 cannot use the
-        # 256-wide kernel that move pays for; the LayerNorm got 20 us slower per call, the GEMMs 3 us faster).
-        Mg = _round_up(M, ROWPAD) if self.dtype == torch.bfloat16 else M
+        # fp32 (bf16 in the bf16 mode) residual stream x / x1 and q|k|v; LayerNorm output, attention context and MLP hidden through act()
+        y, ao, h = self.act("vy", M, D), self.act("vao", M, D), self.act("vh", M, s.v_mlp)
+        qkv, x1 = self.buf("vqkv", M, 3 * D), self.buf("vx1", M, D)
+        # The residual adds ride on the GEMM epilogues (addend): moving them onto the next LayerNorm, as the ViT-B encoder in engine.py
+        # does, measured slower here (N = 1408 cannot use the 256-wide kernel that move pays for; the LayerNorm got 20 us slower per
+        # call, the GEMMs 3 us faster).
+        Mg = self._tile_rows(M)
         if Mg > M:
             x[M:Mg].zero_()          # the padding rows of the residual stream would otherwise carry over from the last pass
         for i in range(s.v_layers):
             p = f"vision_model.encoder.layers.{i}."
             self._ln(x, None, p + "layer_norm1", y, M, D, s.v_eps)
             self._lin(y, p + "self_attn.qkv.weight", p + "self_attn.qkv.bias", qkv, Mg, 3 * D, D)
-            L.mha_cross_fwd(qkv, 3 * D, qkv[:, D:], 3 * D, qkv[:, 2 * D:], 3 * D, ao, D, B, s.v_heads, T, T, dh, dh ** -0.5,
-                            self.dt, self.attn_impl)
+            self._attn(qkv, 3 * D, qkv[:, D:], 3 * D, qkv[:, 2 * D:], 3 * D, ao, D, B, s.v_heads, T, T, dh)
             self._lin(ao, p + "self_attn.projection.weight", p + "self_attn.projection.bias", x1, Mg, D, D, addend=x)      # :395
             self._ln(x1, None, p + "layer_norm2", y, M, D, s.v_eps)
             self._lin(y, p + "mlp.fc1.weight", p + "mlp.fc1.bias", h, Mg, s.v_mlp, D, act=L.ACT_GELU)
             self._lin(h, p + "mlp.fc2.weight", p + "mlp.fc2.bias", x, Mg, D, s.v_mlp, addend=x1)                           # :401
-        emb = self.buf("image_embeds", M, D)
+        emb = self.act("image_embeds", M, D)      # (its only readers are the Q-Former's K|V projections)
         self._ln(x, None, "vision_model.post_layernorm", emb, M, D, s.v_eps)                                               # :521
         return emb
 
-    def _vision_layers_x3(self, x, B):
-        """the 39 layers + post_layernorm of vision_forward in the bf16x3 form: fp32 residual stream x, LayerNorm outputs / attention
-        context / MLP hidden as bf16 plane pairs, q|k|v fp32 (the attention splits them while staging).  Returns image_embeds as a
-        plane pair (its only readers are the Q-Former's K|V projections)."""
-        s = self.s
-        D, T = s.v_dim, s.v_tokens
-        M = B * T
-        Mg = _round_up(M, ROWPAD)
-        dh = D // s.v_heads
-        yp, aop, hp = self.pbuf("vy", M, D), self.pbuf("vao", M, D), self.pbuf("vh", M, s.v_mlp)
-        qkv, x1 = self.buf("vqkv", M, 3 * D), self.buf("vx1", M, D)
-        if Mg > M:
-            x[M:Mg].zero_()
-        for i in range(s.v_layers):
-            p = f"vision_model.encoder.layers.{i}."
-            self._ln3(x, None, p + "layer_norm1", None, yp, M, D, s.v_eps)
-            self._lin3(yp, p + "self_attn.qkv.weight", p + "self_attn.qkv.bias", qkv, Mg, 3 * D, D)
-            L.mha_cross_fwd_x3(qkv, 3 * D, qkv[:, D:], 3 * D, qkv[:, 2 * D:], 3 * D, aop, D, B, s.v_heads, T, T, dh, dh ** -0.5)
-            self._lin3(aop, p + "self_attn.projection.weight", p + "self_attn.projection.bias", x1, Mg, D, D, addend=x)
-            self._ln3(x1, None, p + "layer_norm2", None, yp, M, D, s.v_eps)
-            self._lin3(yp, p + "mlp.fc1.weight", p + "mlp.fc1.bias", hp, Mg, s.v_mlp, D, act=L.ACT_GELU)
-            self._lin3(hp, p + "mlp.fc2.weight", p + "mlp.fc2.bias", x, Mg, D, s.v_mlp, addend=x1)
-        emb = self.pbuf("image_embeds", M, D)
-        self._ln3(x, None, "vision_model.post_layernorm", None, emb, M, D, s.v_eps)
-        return emb
-
-    def _qformer_forward_x3(self, emb, B: int, drop_seed: int):
-        """qformer_forward in the bf16x3 form (emb: the image tokens as a plane pair)"""
+    def qformer_forward(self, image_embeds: Union[torch.Tensor, Planes], B: int, drop_seed: int = 0) -> torch.Tensor:
+        """Blip2QFormerModel.forward with query_embeds = query_tokens.expand(B) and an all-ones image mask
+        (modeling_blip_2.py:889-950, called at :1633-1639 region of Blip2ForConditionalGeneration.get_image_features).
+        image_embeds: what vision_forward returned.  Returns last_hidden_state [B*32 (row-padded), 768].  Dropout (hidden 0.1,
+        attention 0.1) is active in train mode."""
         s = self.s
         Q, NQ, T, D = s.q_dim, s.n_query, s.v_tokens, s.v_dim
         M, Mi = B * NQ, B * T
-        hp_, ap = (s.hidden_drop, s.attn_drop) if self.training else (0.0, 0.0)
+        hp, ap = (s.hidden_drop, s.attn_drop) if self.training else (0.0, 0.0)
         H, dh = s.q_heads, Q // s.q_heads
         sd = lambda layer, site: self._site_seed(drop_seed, layer, site)
         qe = self.buf("q_embed", M, Q)
         qe[:M].view(B, NQ, Q).copy_(self.store.view("query_tokens").expand(B, NQ, Q))
-        hcur, hnext = self.buf("q_h0", M, Q), self.buf("q_h1", M, Q)
-        hcp, hnp = self.pbuf("q_h0p", M, Q), self.pbuf("q_h1p", M, Q)
-        self._ln3(qe, None, "qformer.layernorm", hcur, hcp, M, Q, s.q_eps, out_drop=(hp_, sd(0, 0)))
+        hcur, hnext = self.hidden("q_h0", M, Q), self.hidden("q_h1", M, Q)
+        self._ln(qe, None, "qformer.layernorm", hcur, M, Q, s.q_eps, out_drop=(hp, sd(0, 0)))                             # :912-913
         qkv, o, cq, ckv = self.buf("q_qkv", M, 3 * Q), self.buf("q_o", M, Q), self.buf("q_cq", M, Q), self.buf("q_ckv", Mi, 2 * Q)
-        aop, ffp = self.pbuf("q_ao", M, Q), self.pbuf("q_ff", M, s.q_mlp)
-        for i in range(s.q_layers):
-            p = f"qformer.encoder.layer.{i}."
-            self._lin3(hcp, p + "attention.attention.query.weight", p + "attention.attention.query.bias", qkv, M, 3 * Q, Q, wnumel=3 * Q * Q)
-            L.mha_cross_fwd_x3(qkv, 3 * Q, qkv[:, Q:], 3 * Q, qkv[:, 2 * Q:], 3 * Q, aop, Q, B, H, NQ, NQ, dh, dh ** -0.5, drop_p=ap,
-                               drop_seed=sd(i + 1, 1))
-            self._lin3(aop, p + "attention.output.dense.weight", p + "attention.output.dense.bias", o, M, Q, Q)
-            self._ln3(o, hcur, p + "attention.output.LayerNorm", hnext, hnp, M, Q, s.q_eps, in_drop=(hp_, sd(i + 1, 2)))
-            hcur, hnext, hcp, hnp = hnext, hcur, hnp, hcp
-            if i % s.cross_freq == 0:
-                self._lin3(hcp, p + "crossattention.attention.query.weight", p + "crossattention.attention.query.bias", cq, M, Q, Q)
-                self._lin3(emb, p + "crossattention.attention.key.weight", p + "crossattention.attention.key.bias", ckv, _round_up(Mi, ROWPAD),
-                           2 * Q, D, wnumel=2 * Q * D)
-                L.mha_cross_fwd_x3(cq, Q, ckv, 2 * Q, ckv[:, Q:], 2 * Q, aop, Q, B, H, NQ, T, dh, dh ** -0.5, drop_p=ap, drop_seed=sd(i + 1, 3))
-                self._lin3(aop, p + "crossattention.output.dense.weight", p + "crossattention.output.dense.bias", o, M, Q, Q)
-                self._ln3(o, hcur, p + "crossattention.output.LayerNorm", hnext, hnp, M, Q, s.q_eps, in_drop=(hp_, sd(i + 1, 4)))
-                hcur, hnext, hcp, hnp = hnext, hcur, hnp, hcp
-            self._lin3(hcp, p + "intermediate_query.dense.weight", p + "intermediate_query.dense.bias", ffp, M, s.q_mlp, Q, act=L.ACT_GELU)
-            self._lin3(ffp, p + "output_query.dense.weight", p + "output_query.dense.bias", o, M, Q, s.q_mlp)
-            self._ln3(o, hcur, p + "output_query.LayerNorm", hnext, hnp, M, Q, s.q_eps, in_drop=(hp_, sd(i + 1, 5)))
-            hcur, hnext, hcp, hnp = hnext, hcur, hnp, hcp
-        return hcur
-
-    def qformer_forward(self, image_embeds: torch.Tensor, B: int, drop_seed: int = 0) -> torch.Tensor:
-        """Blip2QFormerModel.forward with query_embeds = query_tokens.expand(B) and an all-ones image mask
-        (modeling_blip_2.py:889-950, called at :1633-1639 region of Blip2ForConditionalGeneration.get_image_features).
-        Returns last_hidden_state [B*32 (row-padded), 768].  Dropout (hidden 0.1, attention 0.1) is active in train mode."""
-        if self.x3:
-            return self._qformer_forward_x3(image_embeds, B, drop_seed)
-        s = self.s
-        Q, NQ, T, D = s.q_dim, s.n_query, s.v_tokens, s.v_dim
-        M, Mi = B * NQ, B * T
-        hp = s.hidden_drop if self.training else 0.0
-        ap = s.attn_drop if self.training else 0.0
-        H, dh = s.q_heads, Q // s.q_heads
-        qe = self.buf("q_embed", M, Q)
-        qe[:M].view(B, NQ, Q).copy_(self.store.view("query_tokens").expand(B, NQ, Q))
-        hcur, hnext = self.buf("q_h0", M, Q), self.buf("q_h1", M, Q)
-        self._ln(qe, None, "qformer.layernorm", hcur, M, Q, s.q_eps, out_drop=(hp, self._site_seed(drop_seed, 0, 0)))    # :912-913
-        qkv, ao, o = self.buf("q_qkv", M, 3 * Q), self.buf("q_ao", M, Q), self.buf("q_o", M, Q)
-        cq, ckv = self.buf("q_cq", M, Q), self.buf("q_ckv", Mi, 2 * Q)
-        ff = self.buf("q_ff", M, s.q_mlp)
+        ao, ff = self.act("q_ao", M, Q), self.act("q_ff", M, s.q_mlp)
         for i in range(s.q_layers):
             p = f"qformer.encoder.layer.{i}."
             # self-attention over the 32 queries (:701-712, 561-606, 616-620)
-            self._lin(hcur, p + "attention.attention.query.weight", p + "attention.attention.query.bias", qkv, M, 3 * Q, Q, wnumel=3 * Q * Q)
-            L.mha_cross_fwd(qkv, 3 * Q, qkv[:, Q:], 3 * Q, qkv[:, 2 * Q:], 3 * Q, ao, Q, B, H, NQ, NQ, dh, dh ** -0.5, self.dt,
-                            self.attn_impl, drop_p=ap, drop_seed=self._site_seed(drop_seed, i + 1, 1))
+            self._lin(hcur.op, p + "attention.attention.query.weight", p + "attention.attention.query.bias", qkv, M, 3 * Q, Q, wnumel=3 * Q * Q)
+            self._attn(qkv, 3 * Q, qkv[:, Q:], 3 * Q, qkv[:, 2 * Q:], 3 * Q, ao, Q, B, H, NQ, NQ, dh, drop_p=ap, drop_seed=sd(i + 1, 1))
             self._lin(ao, p + "attention.output.dense.weight", p + "attention.output.dense.bias", o, M, Q, Q)
-            self._ln(o, hcur, p + "attention.output.LayerNorm", hnext, M, Q, s.q_eps, in_drop=(hp, self._site_seed(drop_seed, i + 1, 2)))
+            self._ln(o, hcur.res, p + "attention.output.LayerNorm", hnext, M, Q, s.q_eps, in_drop=(hp, sd(i + 1, 2)))
             hcur, hnext = hnext, hcur
             if i % s.cross_freq == 0:
                 # cross-attention of the queries to the image tokens (:717-727)
-                self._lin(hcur, p + "crossattention.attention.query.weight", p + "crossattention.attention.query.bias", cq, M, Q, Q)
+                self._lin(hcur.op, p + "crossattention.attention.query.weight", p + "crossattention.attention.query.bias", cq, M, Q, Q)
                 self._lin(image_embeds, p + "crossattention.attention.key.weight", p + "crossattention.attention.key.bias", ckv,
-                          _round_up(Mi, ROWPAD) if self.dtype == torch.bfloat16 else Mi, 2 * Q, D, wnumel=2 * Q * D)
-                L.mha_cross_fwd(cq, Q, ckv, 2 * Q, ckv[:, Q:], 2 * Q, ao, Q, B, H, NQ, T, dh, dh ** -0.5, self.dt, self.attn_impl,
-                                drop_p=ap, drop_seed=self._site_seed(drop_seed, i + 1, 3))
+                          self._tile_rows(Mi), 2 * Q, D, wnumel=2 * Q * D)
+                self._attn(cq, Q, ckv, 2 * Q, ckv[:, Q:], 2 * Q, ao, Q, B, H, NQ, T, dh, drop_p=ap, drop_seed=sd(i + 1, 3))
                 self._lin(ao, p + "crossattention.output.dense.weight", p + "crossattention.output.dense.bias", o, M, Q, Q)
-                self._ln(o, hcur, p + "crossattention.output.LayerNorm", hnext, M, Q, s.q_eps,
-                         in_drop=(hp, self._site_seed(drop_seed, i + 1, 4)))
+                self._ln(o, hcur.res, p + "crossattention.output.LayerNorm", hnext, M, Q, s.q_eps, in_drop=(hp, sd(i + 1, 4)))
                 hcur, hnext = hnext, hcur
             # feed-forward of the query branch (:729-735, 758-761)
-            self._lin(hcur, p + "intermediate_query.dense.weight", p + "intermediate_query.dense.bias", ff, M, s.q_mlp, Q, act=L.ACT_GELU)
+            self._lin(hcur.op, p + "intermediate_query.dense.weight", p + "intermediate_query.dense.bias", ff, M, s.q_mlp, Q, act=L.ACT_GELU)
             self._lin(ff, p + "output_query.dense.weight", p + "output_query.dense.bias", o, M, Q, s.q_mlp)
-            self._ln(o, hcur, p + "output_query.LayerNorm", hnext, M, Q, s.q_eps, in_drop=(hp, self._site_seed(drop_seed, i + 1, 5)))
+            self._ln(o, hcur.res, p + "output_query.LayerNorm", hnext, M, Q, s.q_eps, in_drop=(hp, sd(i + 1, 5)))
             hcur, hnext = hnext, hcur
-        return hcur
+        return hcur.res
 
     def features(self, pixel_values: torch.Tensor, drop_seed: Optional[int] = None) -> torch.Tensor:
         """``outputs['qformer_outputs'].last_hidden_state[:, 0, :]`` (q_former_training.py:290) as fp32 [B, 768]."""

@@ -8,6 +8,7 @@ encoder keys are those of ``transformers`` ``DistilBertModel`` / ``BertModel`` /
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
 from typing import Dict, List, Tuple
 
@@ -119,6 +120,7 @@ def text_params(s: TextSpec) -> List[Tuple[str, Shape]]:
     return P
 
 
+@functools.lru_cache(maxsize=None)      # (asked for by every layer of every forward and backward; callers only read the dict)
 def text_layer_keys(s: TextSpec, i: int) -> Dict[str, str]:
     """Canonical role -> key prefix for layer i."""
     if s.name == "distilbert":
