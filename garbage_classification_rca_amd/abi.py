@@ -1,9 +1,10 @@
 """The C ABI of libmmrca.so as include/mmrca.h declares it: prototypes as ctypes types, struct field names, enum values.
 
-The header is the one checked statement of a signature: tests/test_lib_abi_cpu.py holds lib.py's hand-written ctypes table and every
-wrapper's launch arguments against these prototypes without a GPU, and lib.py's conv byte table reads launch arguments by the
-parameter names found here (profiled launches only; lib.load() itself does not read the header).  The parser accepts only the grammar
-the header's "Conventions" comment states and raises on anything else -- nothing is guessed.  Imports neither torch nor lib.py.
+The header is the one statement of a signature.  lib.load() and jpeg.py type their shared objects from these prototypes (bind), so
+no second table exists in Python; the compiler holds every definition in csrc/ to the same header.  tests/test_lib_abi_cpu.py holds
+the loaded library and every wrapper's launch arguments against the prototypes without a GPU, and lib.py's conv byte table reads
+launch arguments by the parameter names found here.  The parser accepts only the grammar the header's "Conventions" comment states
+and raises on anything else -- nothing is guessed.  Imports neither torch nor lib.py.
 """
 import ctypes as C
 import os
@@ -91,3 +92,15 @@ def parse(header_path=HEADER_PATH, struct_pointers=None) -> Header:
 def prototypes(header_path=HEADER_PATH, struct_pointers=None) -> dict:
     """name -> (restype, [(ctype, parameter name), ...]) of every function the header declares"""
     return parse(header_path, struct_pointers).functions
+
+
+def bind(cdll, functions) -> None:
+    """set restype and argtypes of every function of `functions` (name -> prototype, as prototypes() gives them) on the loaded
+    shared object: a call through it is then converted and range-checked as the header declares"""
+    for name, (restype, params) in functions.items():
+        try:
+            fn = getattr(cdll, name)
+        except AttributeError:
+            raise MmrcaError(f"{name} is declared in the header but {getattr(cdll, '_name', 'the shared object')} does not export it: "
+                             "rebuild the library (__graft_entry__.build())") from None
+        fn.restype, fn.argtypes = restype, [ctype for ctype, _ in params]

@@ -9,8 +9,8 @@ never exist in host memory.  The result is byte-identical to ``PIL.Image.open(..
 Whatever the host decoder does not handle exactly (progressive, CMYK, odd samplings, damaged files, non-JPEG files) it DECLINES,
 and the worker decodes that one file with Pillow as ``main_both.DecodeOnly`` does; such stragglers ride along in the batch.
 
-Opt-in: ``MMRCA_GPU_JPEG=1`` together with ``--gpu_preprocess`` (``main_both.decode_only``).  ctypes prototypes come from the
-header through ``abi.prototypes``, as lib.py's are checked against mmrca.h."""
+Opt-in: ``MMRCA_GPU_JPEG=1`` together with ``--gpu_preprocess`` (``main_both.decode_only``).  Both shared objects are typed from the
+header by ``abi.bind``, as lib.py types libmmrca.so from mmrca.h."""
 from __future__ import annotations
 
 import ctypes as C
@@ -62,11 +62,9 @@ def _constants() -> dict:
     return _enum_values
 
 
-def _typed(lib, name):
-    restype, params = header().functions[name]
-    fn = getattr(lib, name)
-    fn.restype, fn.argtypes = restype, [t for t, _ in params]
-    return fn
+def _bind(lib, names):
+    """the header's prototypes of `names` on a loaded shared object (abi.MmrcaError names a function it lacks)"""
+    abi.bind(lib, {name: header().functions[name] for name in names})
 
 
 def load_host():
@@ -76,8 +74,7 @@ def load_host():
         if not os.path.exists(LIB_PATH):
             raise JpegError(f"{LIB_PATH} not found: build it with __graft_entry__.build() (make -C garbage_classification_rca_amd/csrc)")
         lib = C.CDLL(LIB_PATH)
-        for name in HOST_FUNCTIONS:
-            _typed(lib, name)
+        _bind(lib, HOST_FUNCTIONS)
         _host = lib
     return _host
 
@@ -228,7 +225,8 @@ def idct_rgb(coef: torch.Tensor, desc: torch.Tensor, n_images: int, out: torch.T
     global _device_fn
     from . import lib as L
     if _device_fn is None:
-        _device_fn = _typed(L.load(), "mmrca_jpeg_idct_rgb")
+        _bind(L.load(), DEVICE_FUNCTIONS)
+        _device_fn = L.load().mmrca_jpeg_idct_rgb
     for t, dt, name in ((coef, torch.int16, "coef"), (desc, torch.uint8, "desc"), (out, torch.uint8, "out")):
         if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
             raise JpegError(f"idct_rgb: {name} must be a contiguous {dt} tensor in HBM")

@@ -8,9 +8,12 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
+
+from . import abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmmrca.so")
@@ -46,121 +49,23 @@ def build_library(force: bool = False) -> str:
 
 
 _lib = None
+_protos = None
 
-_i64, _i32, _f32, _vp, _u64 = C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_uint64
-_SIGS = {
-    "mmrca_gemm": [_vp] * 6 + [_i64] * 6 + [_i32] * 6 + [_vp],
-    "mmrca_gemm_colsum": [_vp] * 7 + [_i64] * 6 + [_i32] * 5 + [_vp],
-    "mmrca_gemm_rows": [_vp] * 7 + [_i64] * 8 + [_i32] * 5 + [_vp],
-    "mmrca_gemm_splitk": [_vp] * 4 + [_i64] * 7 + [_i32] * 2 + [_vp],
-    "mmrca_gemm_streamk_workspace": [_vp, _i64, _vp],
-    "mmrca_gemm_streamk_config": [_i32, _i32, _i32],
-    "mmrca_gemm_x3": [_vp] * 10 + [_i64] * 6 + [_i32] * 5 + [_vp],
-    "mmrca_gemm_splitk_x3": [_vp] * 6 + [_i64] * 7 + [_i32] * 2 + [_vp],
-    "mmrca_split_f32": [_vp, _vp, _vp, _i64, _vp],
-    "mmrca_sgd_step_x3": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp],
-    "mmrca_adamw_step_x3": [_vp] * 6 + [_i64] + [_f32] * 5 + [_i32, _f32, _vp],
-    "mmrca_nchw_to_rows": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_im2row3x3": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp],
-    "mmrca_col2im3x3": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp],
-    "mmrca_im2row3x3_tap": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp],
-    "mmrca_col2im3x3_tap": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i32, _vp],
-    "mmrca_dwconv3x3_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_dwconv3x3_bwd_ws": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    "mmrca_dwconv3x3_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_dwconv5x5_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_dwconv5x5_bwd_ws": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
-    "mmrca_conv3x3_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_conv_bn_finish": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp],
-    "mmrca_conv3x3_wgrad": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_gemm_bnstats": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
-    "mmrca_bn_finish_sums": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp],
-    "mmrca_bn_act_bwd_sums": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_se_dx": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
-    "mmrca_bn_act_fwd_res": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _vp],
-    "mmrca_bn_moments": [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i32, _vp],
-    "mmrca_bn_act_fwd_fin": [_vp] * 13 + [_i64, _i32, _i32, _i64, _f32, _f32, _i32, _vp],
-    "mmrca_bn_stats": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _f32, _f32, _i32, _i32, _vp],
-    "mmrca_bn_stats_ws": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _f32, _f32, _i32, _i32, _vp, _i64, _i32, _vp],
-    "mmrca_bn_stats_fused": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _f32, _f32, _i32, _vp, _i32, _vp],
-    "mmrca_bn_act_bwd_ws": [_vp] * 10 + [_i64, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp],
-    "mmrca_bn_act_fwd": [_vp] * 6 + [_i64, _i32, _i32, _i32, _vp],
-    "mmrca_bn_act_bwd": [_vp] * 10 + [_i64, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_rowpool_mean": [_vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_rowpool_mean_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_se_scale_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_se_mlp_fwd": [_vp] * 9 + [_i32] * 4 + [_vp],
-    "mmrca_se_mlp_bwd": [_vp] * 16 + [_i32] * 4 + [_vp],
-    "mmrca_se_scale_bwd": [_vp] * 5 + [_i32, _i32, _i32, _i32, _vp],
-    "mmrca_bias_act_fwd": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "mmrca_bias_act_bwd": [_vp] * 5 + [_i64, _i32, _i32, _i32, _vp],
-    "mmrca_residual_add": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp],
-    "mmrca_maxpool3x3s2_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_maxpool3x3s2_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_channel_gather": [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _i32, _vp],
-    "mmrca_channel_interleave2": [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp],
-    "mmrca_channel_deinterleave2": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
-    "mmrca_image_preprocess": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    "mmrca_image_rotate_crop": [_vp, _vp, _i32, _i32, _vp],
-    "mmrca_image_resize_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _vp],
-    "mmrca_image_stats_u8": [_vp, _vp, _vp, _i32, _i32, _i32, _vp],
-    "mmrca_image_augment": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    "mmrca_colsum_accum": [_vp, _vp, _i64, _i64, _i64, _i32, _vp],
-    "mmrca_gelu_bwd": [_vp, _vp, _vp, _i64, _i32, _vp],
-    "mmrca_gelu_bwd_colsum": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp],
-    "mmrca_mha_fwd": [_vp] * 4 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _i32, _i32, _vp],
-    "mmrca_mha_fwd_planes": [_vp] * 6 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _vp],
-    "mmrca_mha_fwd_planes_in": [_vp] * 7 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _vp],
-    "mmrca_mha_fwd_x3": [_vp] * 6 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _vp],
-    "mmrca_mha_bwd": [_vp] * 6 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _i32, _i32, _vp],
-    "mmrca_mha_bwd_colsum": [_vp] * 7 + [_i64] + [_i32] * 4 + [_f32, _f32, _u64, _vp, _i32, _i32, _vp],
-    "mmrca_mha_cross_fwd": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64] + [_i32] * 5 + [_f32, _f32, _u64, _i32, _i32, _vp],
-    "mmrca_mha_cross_fwd_x3": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64] + [_i32] * 5 + [_f32, _f32, _u64, _vp],
-    "mmrca_mha_cls_fwd": [_vp] * 4 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _i32, _vp],
-    "mmrca_mha_cls_bwd": [_vp] * 6 + [_i32] * 4 + [_f32, _f32, _u64, _vp, _i32, _vp],
-    "mmrca_add_layernorm_fwd": [_vp] * 8 + [_i64, _i32, _i64, _i64, _f32, _f32, _u64, _f32, _u64, _i32, _vp],
-    "mmrca_add_layernorm_fwd_x3": [_vp] * 10 + [_i64, _i32, _i64, _i64, _f32, _f32, _u64, _f32, _u64, _vp],
-    "mmrca_layernorm_bwd": [_vp] * 9 + [_i64, _i32, _i64, _i64, _i64, _f32, _u64, _f32, _u64, _vp, _vp, _vp, _i32, _vp],
-    "mmrca_layernorm_bwd_mixed": [_vp] * 9 + [_i64, _i32, _i64, _i64, _i64, _f32, _u64, _f32, _u64, _vp, _vp, _vp, _vp],
-    "mmrca_embed_fwd": [_vp] * 6 + [_i64, _i32, _i32, _vp],
-    "mmrca_embed_bwd": [_vp] * 6 + [_i64, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_patchify_fwd": [_vp, _vp] + [_i32] * 6 + [_vp],
-    "mmrca_vit_assemble_fwd": [_vp] * 4 + [_i32] * 4 + [_vp],
-    "mmrca_vit_assemble_bwd": [_vp] * 4 + [_i32] * 4 + [_vp],
-    "mmrca_head_fwd": [_vp, _vp, C.POINTER(HeadPtrs), _vp] + [_i32] * 6 + [_f32, _u64, _i32, _vp],
-    "mmrca_head_bwd": [_vp, _vp, _vp, C.POINTER(HeadPtrs), C.POINTER(HeadPtrs), _vp, _vp] + [_i32] * 6 + [_f32, _u64, _i32, _vp, _i64, _vp],
-    "mmrca_xent_fwd_bwd": [_vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _f32, _vp],
-    "mmrca_sgd_step": [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _vp],
-    "mmrca_adamw_step": [_vp] * 5 + [_i64] + [_f32] * 5 + [_i32, _f32, _vp],
-    "mmrca_cast_f32_to_bf16": [_vp, _vp, _i64, _vp],
-    "mmrca_seed_epoch_set": [_vp, _u64, _vp],
-    "mmrca_linear_cls_fwd": [_vp, _i32, _vp, _vp, _vp] + [_i32] * 3 + [_f32, _u64, _i32, _vp],
-    "mmrca_linear_cls_bwd": [_vp, _vp, _i32, _vp, _vp, _vp, _vp] + [_i32] * 3 + [_f32, _u64, _i32, _vp],
-    "mmrca_sd_rowscale": [_vp, _vp, _i32, _i32, _u64, _vp],
-    "mmrca_hier_pool_fwd": [_vp, _vp] + [_i32] * 7 + [_vp],
-    "mmrca_hier_pool_bwd": [_vp, _i32, _vp] + [_i32] * 6 + [_vp],
-    "mmrca_hier_norm_fwd": [_vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _u64, _u64, _vp],
-    "mmrca_hier_norm_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _u64, _u64, _vp],
-    "mmrca_hier_linear_relu_fwd": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
-    "mmrca_hier_linear_relu_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
-    "mmrca_gru_linear_fwd": [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_gru_linear_bwd": [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "mmrca_gru_fwd": [_i32] + [_vp] * 6 + [_i32, _i32, _vp],
-    "mmrca_gru_bwd": [_i32] + [_vp] * 9 + [_i32, _i32, _vp],
-    "mmrca_hadamard_fwd": [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
-    "mmrca_hadamard_bwd": [_vp, _i32] * 5 + [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp],
-    "mmrca_dropout_f32": [_vp, _i32, _vp, _i32, _i32, _i32, _f32, _u64, _vp],
-    "mmrca_nonorm_fwd": [_vp] * 6 + [_i64, _i32] + [_i64] * 4 + [_i32, _vp],
-    "mmrca_nonorm_bwd": [_vp] * 9 + [_i64, _i64, _i32] + [_i64] * 4 + [_i32, _vp],
-    "mmrca_trigram_embed_fwd": [_vp] * 4 + [_i64] + [_i32] * 5 + [_vp],
-    "mmrca_trigram_embed_bwd": [_vp] * 4 + [_i64] + [_i32] * 6 + [_vp],
-}
-EXPORTS = sorted(list(_SIGS) + ["mmrca_last_error", "mmrca_version", "mmrca_debug_set", "mmrca_bn_flat_set", "mmrca_debug_attn_stamps", "mmrca_gemm_splitk_workspace_bytes", "mmrca_gemm_streamk_workspace_bytes",
-                                  "mmrca_head_bwd_workspace_bytes", "mmrca_conv3x3_stat_slots", "mmrca_gemm_bnstats_slots",
-                                  "mmrca_hier_linear_workspace_bytes", "mmrca_nonorm_bwd_workspace_bytes"])
+
+def _prototypes():
+    """include/mmrca.h as abi.py reads it, parsed once per process: entry point -> (restype, [(ctype, parameter name), ...])"""
+    global _protos
+    if _protos is None:
+        head = C.POINTER(HeadPtrs)
+        try:
+            _protos = abi.prototypes(struct_pointers={"MmrcaHeadWeights": head, "MmrcaHeadGrads": head})
+        except abi.MmrcaError as e:
+            raise MmrcaError(str(e)) from None
+    return _protos
 
 
 def load(build_if_missing: bool = False):
+    """libmmrca.so with every function the header declares typed as the header declares it"""
     global _lib
     if _lib is not None:
         return _lib
@@ -171,22 +76,10 @@ def load(build_if_missing: bool = False):
             raise MmrcaError(f"{LIB_PATH} not found: the HIP extension is required (run __graft_entry__.build()); "
                              "there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    for name, args in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int
-    lib.mmrca_gemm_splitk_workspace_bytes.argtypes = [_i64, _i64]
-    lib.mmrca_gemm_splitk_workspace_bytes.restype = _i64
-    lib.mmrca_gemm_streamk_workspace_bytes.argtypes = []
-    lib.mmrca_gemm_streamk_workspace_bytes.restype = _i64
-    lib.mmrca_hier_linear_workspace_bytes.argtypes = [_i32, _i32, _i32]
-    lib.mmrca_hier_linear_workspace_bytes.restype = _i64
-    lib.mmrca_nonorm_bwd_workspace_bytes.argtypes = [_i64, _i32]
-    lib.mmrca_nonorm_bwd_workspace_bytes.restype = _i64
-    lib.mmrca_conv3x3_stat_slots.argtypes = [_i32, _i32, _i32]
-    lib.mmrca_conv3x3_stat_slots.restype = _i64
-    lib.mmrca_last_error.restype = C.c_char_p
-    lib.mmrca_version.restype = C.c_int
+    try:
+        abi.bind(lib, _prototypes())
+    except abi.MmrcaError as e:
+        raise MmrcaError(str(e)) from None
     _lib = lib
     return lib
 
@@ -223,6 +116,15 @@ def stream_ptr() -> int:
 def _dev(t: torch.Tensor, name: str):
     if not t.is_cuda:
         raise MmrcaError(f"{name}: tensor must live in HBM (got device {t.device}); the product path has no CPU fallback")
+
+
+def _launch(name, *args):
+    """entry point `name` on the current stream, which every launching prototype takes last; a failure raises under that name.
+    = _check(getattr(load(), name)(*args, stream_ptr()), name), without the frames of load() and _check on the way every launch but
+    the first and a failed one go: they pay for the frame of this helper"""
+    rc = getattr(_lib if _lib is not None else load(), name)(*args, stream_ptr())
+    if rc != 0:
+        _check(rc, name)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -284,7 +186,7 @@ def streamk_workspace(M, N, device, force=False):
         return      # a capture stream meets its first large product: no allocation / fill inside the capture -- it keeps the two-launch split
     need = int(load().mmrca_gemm_streamk_workspace_bytes())
     ws = torch.zeros(need, dtype=torch.uint8, device=device)
-    _check(load().mmrca_gemm_streamk_workspace(ptr(ws), need, st), "mmrca_gemm_streamk_workspace")
+    _launch("mmrca_gemm_streamk_workspace", ptr(ws), need)      # on the current stream = st: nothing above changes it
     _STREAMK_WS[key] = ws
 
 
@@ -301,9 +203,8 @@ def gemm(A, B, Cout, *, bias=None, addend=None, preact=None, M, N, K, lda, ldb, 
     if rows_readable is not None:
         if accum:
             raise MmrcaError("gemm: rows_readable is not available in accumulate mode")
-        _check(load().mmrca_gemm_rows(ptr(A), ptr(B), ptr(Cout), ptr(bias), ptr(addend), ptr(preact), ptr(colsum), M, N, K, lda, ldb, ldc,
-                                      int(rows_readable[0]), int(rows_readable[1]), a_layout, b_layout, act, dtype, impl, stream_ptr()),
-               "mmrca_gemm_rows")
+        _launch("mmrca_gemm_rows", ptr(A), ptr(B), ptr(Cout), ptr(bias), ptr(addend), ptr(preact), ptr(colsum), M, N, K, lda, ldb, ldc,
+                int(rows_readable[0]), int(rows_readable[1]), a_layout, b_layout, act, dtype, impl)
         return
     # matrix-core launches: the bf16 MFMA kernels, and in fp32 mode the general kernel on the fp32 matrix cores
     prof = GEMM_PROFILE is not None and (gemm_is_mfma(M, N, K, a_layout, dtype, impl) or (dtype == F32 and impl != IMPL_REF))
@@ -313,11 +214,11 @@ def gemm(A, B, Cout, *, bias=None, addend=None, preact=None, M, N, K, lda, ldb, 
     if colsum is not None:
         if accum:
             raise MmrcaError("gemm: colsum is not available in accumulate mode")
-        _check(load().mmrca_gemm_colsum(ptr(A), ptr(B), ptr(Cout), ptr(bias), ptr(addend), ptr(preact), ptr(colsum), M, N, K,
-                                        lda, ldb, ldc, a_layout, b_layout, act, dtype, impl, stream_ptr()), "mmrca_gemm_colsum")
+        _launch("mmrca_gemm_colsum", ptr(A), ptr(B), ptr(Cout), ptr(bias), ptr(addend), ptr(preact), ptr(colsum), M, N, K, lda, ldb, ldc, a_layout,
+                b_layout, act, dtype, impl)
     else:
-        _check(load().mmrca_gemm(ptr(A), ptr(B), ptr(Cout), ptr(bias), ptr(addend), ptr(preact), M, N, K, lda, ldb, ldc,
-                                 a_layout, b_layout, act, int(accum), dtype, impl, stream_ptr()), "mmrca_gemm")
+        _launch("mmrca_gemm", ptr(A), ptr(B), ptr(Cout), ptr(bias), ptr(addend), ptr(preact), M, N, K, lda, ldb, ldc, a_layout, b_layout, act,
+                int(accum), dtype, impl)
     if timed:
         e1.record()
     if prof:
@@ -351,8 +252,8 @@ def gemm_splitk(A, B, Cout, workspace, *, M, N, K, lda, ldb, ldc, a_layout=KROW,
     prof = GEMM_PROFILE is not None
     if prof:
         e0, e1 = _events()
-    _check(load().mmrca_gemm_splitk(ptr(A), ptr(B), ptr(Cout), ptr(workspace), workspace.numel() * workspace.element_size(),
-                                    M, N, K, lda, ldb, ldc, a_layout, b_layout, stream_ptr()), "mmrca_gemm_splitk")
+    _launch("mmrca_gemm_splitk", ptr(A), ptr(B), ptr(Cout), ptr(workspace), workspace.numel() * workspace.element_size(), M, N, K, lda, ldb, ldc,
+            a_layout, b_layout)
     if prof:
         e1.record()
         GEMM_PROFILE.append((2.0 * M * N * K, (a_layout, b_layout, 1), e0, e1, (M, N, K, ACT_NONE)))
@@ -370,9 +271,8 @@ def gemm_x3(A, B, Cout, *, C_lo=None, bias=None, addend=None, preact=None, colsu
     prof = GEMM_PROFILE is not None
     if prof:
         e0, e1 = _events()
-    _check(load().mmrca_gemm_x3(ptr(A[0]), ptr(A[1]), ptr(B[0]), ptr(B[1]), ptr(Cout), ptr(C_lo), ptr(bias), ptr(addend), ptr(preact),
-                                ptr(colsum), M, N, K, lda, ldb, ldc, a_layout, b_layout, act, int(accum), impl, stream_ptr()),
-           "mmrca_gemm_x3")
+    _launch("mmrca_gemm_x3", ptr(A[0]), ptr(A[1]), ptr(B[0]), ptr(B[1]), ptr(Cout), ptr(C_lo), ptr(bias), ptr(addend), ptr(preact), ptr(colsum), M, N,
+            K, lda, ldb, ldc, a_layout, b_layout, act, int(accum), impl)
     if prof:
         e1.record()
         # three bf16 MFMA passes per product: the executed matrix-core work is 3 x 2MNK
@@ -386,9 +286,8 @@ def gemm_splitk_x3(A, B, Cout, workspace, *, M, N, K, lda, ldb, ldc, a_layout=KR
     prof = GEMM_PROFILE is not None
     if prof:
         e0, e1 = _events()
-    _check(load().mmrca_gemm_splitk_x3(ptr(A[0]), ptr(A[1]), ptr(B[0]), ptr(B[1]), ptr(Cout), ptr(workspace),
-                                       workspace.numel() * workspace.element_size(), M, N, K, lda, ldb, ldc, a_layout, b_layout,
-                                       stream_ptr()), "mmrca_gemm_splitk_x3")
+    _launch("mmrca_gemm_splitk_x3", ptr(A[0]), ptr(A[1]), ptr(B[0]), ptr(B[1]), ptr(Cout), ptr(workspace),
+            workspace.numel() * workspace.element_size(), M, N, K, lda, ldb, ldc, a_layout, b_layout)
     if prof:
         e1.record()
         GEMM_PROFILE.append((6.0 * M * N * K, (a_layout, b_layout, 1), e0, e1, (M, N, K, ACT_NONE)))
@@ -397,27 +296,26 @@ def gemm_splitk_x3(A, B, Cout, workspace, *, M, N, K, lda, ldb, ldc, a_layout=KR
 def split_f32(src, hi, lo, n):
     """hi = bf16(src), lo = bf16(src - hi): the two-plane form of fp32 values the bf16x3 GEMMs read"""
     _dev(src, "split src")
-    _check(load().mmrca_split_f32(ptr(src), ptr(hi), ptr(lo), n, stream_ptr()), "mmrca_split_f32")
+    _launch("mmrca_split_f32", ptr(src), ptr(hi), ptr(lo), n)
 
 
 def colsum_accum(dY, db, M, N, ld, dtype):
-    _check(load().mmrca_colsum_accum(ptr(dY), ptr(db), M, N, ld, dtype, stream_ptr()), "mmrca_colsum_accum")
+    _launch("mmrca_colsum_accum", ptr(dY), ptr(db), M, N, ld, dtype)
 
 
 def gelu_bwd(dG, H, dH, n, dtype):
-    _check(load().mmrca_gelu_bwd(ptr(dG), ptr(H), ptr(dH), n, dtype, stream_ptr()), "mmrca_gelu_bwd")
+    _launch("mmrca_gelu_bwd", ptr(dG), ptr(H), ptr(dH), n, dtype)
 
 
 def gelu_bwd_colsum(dG, H, dH, db, M, N, ld, dtype):
-    _check(load().mmrca_gelu_bwd_colsum(ptr(dG), ptr(H), ptr(dH), ptr(db), M, N, ld, dtype, stream_ptr()), "mmrca_gelu_bwd_colsum")
+    _launch("mmrca_gelu_bwd_colsum", ptr(dG), ptr(H), ptr(dH), ptr(db), M, N, ld, dtype)
 
 
 def mha_fwd(qkv, key_mask, out, lse, B, H, S, dh, scale, dtype, impl=IMPL_AUTO, drop_p=0.0, drop_seed=0, cu=None):
     """cu (int32 [B+1], device): packed token layout, sequence b = rows [cu[b], cu[b+1]); None = padded [B*S] rows"""
     _dev(qkv, "mha qkv")
     with _Bracket("mha_fwd", (B, H, S, dh, cu is not None)):
-        _check(load().mmrca_mha_fwd(ptr(qkv), ptr(key_mask), ptr(out), ptr(lse), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), dtype,
-                                    impl, stream_ptr()), "mmrca_mha_fwd")
+        _launch("mmrca_mha_fwd", ptr(qkv), ptr(key_mask), ptr(out), ptr(lse), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), dtype, impl)
 
 
 def mha_fwd_planes_ok(S, dh):
@@ -428,17 +326,16 @@ def mha_fwd_planes(qkv, key_mask, out, out_planes, lse, B, H, S, dh, scale, drop
     """fp32 attention forward that also writes the context as (hi, lo) bf16 planes (bf16x3 mode)"""
     _dev(qkv, "mha qkv")
     with _Bracket("mha_fwd", (B, H, S, dh, cu is not None)):
-        _check(load().mmrca_mha_fwd_planes(ptr(qkv), ptr(key_mask), ptr(out), ptr(out_planes[0]), ptr(out_planes[1]), ptr(lse), B, H, S, dh,
-                                           scale, drop_p, drop_seed, ptr(cu), stream_ptr()), "mmrca_mha_fwd_planes")
+        _launch("mmrca_mha_fwd_planes", ptr(qkv), ptr(key_mask), ptr(out), ptr(out_planes[0]), ptr(out_planes[1]), ptr(lse), B, H, S, dh, scale,
+                drop_p, drop_seed, ptr(cu))
 
 
 def mha_fwd_planes_in(qkv_planes, key_mask, out, out_planes, lse, B, H, S, dh, scale, drop_p=0.0, drop_seed=0, cu=None):
     """mha_fwd_planes with q|k|v given as (hi, lo) bf16 planes (bf16x3f mode)"""
     _dev(qkv_planes[0], "mha qkv")
     with _Bracket("mha_fwd", (B, H, S, dh, cu is not None)):
-        _check(load().mmrca_mha_fwd_planes_in(ptr(qkv_planes[0]), ptr(qkv_planes[1]), ptr(key_mask), ptr(out), ptr(out_planes[0]),
-                                              ptr(out_planes[1]), ptr(lse), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), stream_ptr()),
-               "mmrca_mha_fwd_planes_in")
+        _launch("mmrca_mha_fwd_planes_in", ptr(qkv_planes[0]), ptr(qkv_planes[1]), ptr(key_mask), ptr(out), ptr(out_planes[0]), ptr(out_planes[1]),
+                ptr(lse), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu))
 
 
 def mha_fwd_x3_ok(S, dh):
@@ -449,8 +346,8 @@ def mha_fwd_x3(qkv_planes, key_mask, out_planes, lse, B, H, S, dh, scale, drop_p
     """bf16x3 attention forward on the bf16 matrix cores: q|k|v and the context as (hi, lo) bf16 planes"""
     _dev(qkv_planes[0], "mha qkv")
     with _Bracket("mha_fwd", (B, H, S, dh, cu is not None)):
-        _check(load().mmrca_mha_fwd_x3(ptr(qkv_planes[0]), ptr(qkv_planes[1]), ptr(key_mask), ptr(out_planes[0]), ptr(out_planes[1]), ptr(lse),
-                                       B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), stream_ptr()), "mmrca_mha_fwd_x3")
+        _launch("mmrca_mha_fwd_x3", ptr(qkv_planes[0]), ptr(qkv_planes[1]), ptr(key_mask), ptr(out_planes[0]), ptr(out_planes[1]), ptr(lse), B, H, S,
+                dh, scale, drop_p, drop_seed, ptr(cu))
 
 
 def mha_bwd(qkv, key_mask, out, dout, lse, dqkv, B, H, S, dh, scale, dtype, impl=IMPL_AUTO, drop_p=0.0, drop_seed=0, colsum=None,
@@ -459,19 +356,17 @@ def mha_bwd(qkv, key_mask, out, dout, lse, dqkv, B, H, S, dh, scale, dtype, impl
     rows = number of token rows (defaults to B*S; pass cu[B] for the packed layout)"""
     with _Bracket("mha_bwd", (B, H, S, dh, cu is not None)):
         if colsum is not None:
-            _check(load().mmrca_mha_bwd_colsum(ptr(qkv), ptr(key_mask), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(colsum),
-                                               B * S if rows is None else rows, B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), dtype,
-                                               impl, stream_ptr()), "mmrca_mha_bwd_colsum")
+            _launch("mmrca_mha_bwd_colsum", ptr(qkv), ptr(key_mask), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), ptr(colsum),
+                    B * S if rows is None else rows, B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), dtype, impl)
             return
-        _check(load().mmrca_mha_bwd(ptr(qkv), ptr(key_mask), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, H, S, dh, scale,
-                                    drop_p, drop_seed, ptr(cu), dtype, impl, stream_ptr()), "mmrca_mha_bwd")
+        _launch("mmrca_mha_bwd", ptr(qkv), ptr(key_mask), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu),
+                dtype, impl)
 
 
 def mha_cross_fwd(q, ldq, k, ldk, v, ldv, out, ldo, B, H, Sq, Skv, dh, scale, dtype, impl=IMPL_AUTO, drop_p=0.0, drop_seed=0):
     """attention forward with separate q / k / v operands (tensors or views; the pointers are taken at their first element)"""
     _dev(q, "q"); _dev(k, "k"); _dev(v, "v"); _dev(out, "out")
-    _check(load().mmrca_mha_cross_fwd(ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(out), ldo, B, H, Sq, Skv, dh, scale, drop_p,
-                                      drop_seed, dtype, impl, stream_ptr()), "mha_cross_fwd")
+    _launch("mmrca_mha_cross_fwd", ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(out), ldo, B, H, Sq, Skv, dh, scale, drop_p, drop_seed, dtype, impl)
 
 
 def mha_cross_fwd_x3(q, ldq, k, ldk, v, ldv, out_planes, ldo, B, H, Sq, Skv, dh, scale, drop_p=0.0, drop_seed=0):
@@ -479,20 +374,19 @@ def mha_cross_fwd_x3(q, ldq, k, ldk, v, ldv, out_planes, ldo, B, H, Sq, Skv, dh,
     _dev(q, "q"); _dev(k, "k"); _dev(v, "v"); _dev(out_planes[0], "out")
     if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32 or out_planes[0].dtype != torch.bfloat16:
         raise MmrcaError("mha_cross_fwd_x3: q / k / v must be fp32 and the output planes bf16")
-    _check(load().mmrca_mha_cross_fwd_x3(ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(out_planes[0]), ptr(out_planes[1]), ldo, B, H, Sq, Skv, dh,
-                                         scale, drop_p, drop_seed, stream_ptr()), "mmrca_mha_cross_fwd_x3")
+    _launch("mmrca_mha_cross_fwd_x3", ptr(q), ldq, ptr(k), ldk, ptr(v), ldv, ptr(out_planes[0]), ptr(out_planes[1]), ldo, B, H, Sq, Skv, dh, scale,
+            drop_p, drop_seed)
 
 
 def mha_cls_fwd(qkv, key_mask, out, lse, B, H, S, dh, scale, dtype, drop_p=0.0, drop_seed=0, cu=None):
     """attention of the class-token query (row 0) only: out [B, H*dh], lse [B, H]"""
     _dev(qkv, "mha_cls qkv")
-    _check(load().mmrca_mha_cls_fwd(ptr(qkv), ptr(key_mask), ptr(out), ptr(lse), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu),
-                                    dtype, stream_ptr()), "mmrca_mha_cls_fwd")
+    _launch("mmrca_mha_cls_fwd", ptr(qkv), ptr(key_mask), ptr(out), ptr(lse), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu), dtype)
 
 
 def mha_cls_bwd(qkv, key_mask, out, dout, lse, dqkv, B, H, S, dh, scale, dtype, drop_p=0.0, drop_seed=0, cu=None):
-    _check(load().mmrca_mha_cls_bwd(ptr(qkv), ptr(key_mask), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, H, S, dh, scale,
-                                    drop_p, drop_seed, ptr(cu), dtype, stream_ptr()), "mmrca_mha_cls_bwd")
+    _launch("mmrca_mha_cls_bwd", ptr(qkv), ptr(key_mask), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, H, S, dh, scale, drop_p, drop_seed, ptr(cu),
+            dtype)
 
 
 def add_layernorm_fwd(x, res, gamma, beta, sum_out, y, mean, rstd, rows, D, ld_x, ld_y, eps, dtype,
@@ -500,67 +394,59 @@ def add_layernorm_fwd(x, res, gamma, beta, sum_out, y, mean, rstd, rows, D, ld_x
     """y_planes = (hi, lo) bf16 tensors (fp32 operands only): the output also -- or, with y None, only -- as two bf16 planes"""
     _dev(x, "layernorm x")
     if y_planes is not None:
-        _check(load().mmrca_add_layernorm_fwd_x3(ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), ptr(y_planes[0]),
-                                                 ptr(y_planes[1]), ptr(mean), ptr(rstd), rows, D, ld_x, ld_y, eps, in_drop[0], in_drop[1],
-                                                 out_drop[0], out_drop[1], stream_ptr()), "mmrca_add_layernorm_fwd_x3")
+        _launch("mmrca_add_layernorm_fwd_x3", ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), ptr(y_planes[0]), ptr(y_planes[1]),
+                ptr(mean), ptr(rstd), rows, D, ld_x, ld_y, eps, in_drop[0], in_drop[1], out_drop[0], out_drop[1])
         return
-    _check(load().mmrca_add_layernorm_fwd(ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), ptr(mean), ptr(rstd),
-                                          rows, D, ld_x, ld_y, eps, in_drop[0], in_drop[1], out_drop[0], out_drop[1],
-                                          dtype, stream_ptr()), "mmrca_add_layernorm_fwd")
+    _launch("mmrca_add_layernorm_fwd", ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), ptr(mean), ptr(rstd), rows, D, ld_x, ld_y, eps,
+            in_drop[0], in_drop[1], out_drop[0], out_drop[1], dtype)
 
 
 def layernorm_bwd(dy, s, gamma, mean, rstd, dres, ds, dgamma, dbeta, rows, D, ld_dy, ld_s, ld_ds, dtype,
                   dy_drop=(0.0, 0), branch_drop=(0.0, 0), dbranch=None, dcol=None, dcol_branch=None):
-    _check(load().mmrca_layernorm_bwd(ptr(dy), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(ds), ptr(dgamma),
-                                      ptr(dbeta), rows, D, ld_dy, ld_s, ld_ds, dy_drop[0], dy_drop[1], branch_drop[0],
-                                      branch_drop[1], ptr(dbranch), ptr(dcol), ptr(dcol_branch), dtype, stream_ptr()), "mmrca_layernorm_bwd")
+    _launch("mmrca_layernorm_bwd", ptr(dy), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(ds), ptr(dgamma), ptr(dbeta), rows, D, ld_dy,
+            ld_s, ld_ds, dy_drop[0], dy_drop[1], branch_drop[0], branch_drop[1], ptr(dbranch), ptr(dcol), ptr(dcol_branch), dtype)
 
 
 def layernorm_bwd_mixed(dy, s, gamma, mean, rstd, dres, ds, dgamma, dbeta, rows, D, ld_dy, ld_s, ld_ds,
                         dy_drop=(0.0, 0), branch_drop=(0.0, 0), dbranch=None, dcol=None, dcol_branch=None):
     """layernorm_bwd with bf16 gradients / gamma against the fp32 saved sum `s` (bf16x3f mode)"""
-    _check(load().mmrca_layernorm_bwd_mixed(ptr(dy), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(ds), ptr(dgamma),
-                                            ptr(dbeta), rows, D, ld_dy, ld_s, ld_ds, dy_drop[0], dy_drop[1], branch_drop[0],
-                                            branch_drop[1], ptr(dbranch), ptr(dcol), ptr(dcol_branch), stream_ptr()), "mmrca_layernorm_bwd_mixed")
+    _launch("mmrca_layernorm_bwd_mixed", ptr(dy), ptr(s), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(ds), ptr(dgamma), ptr(dbeta), rows, D,
+            ld_dy, ld_s, ld_ds, dy_drop[0], dy_drop[1], branch_drop[0], branch_drop[1], ptr(dbranch), ptr(dcol), ptr(dcol_branch))
 
 
 def embed_fwd(ids, pos_ids, word, pos, type_row, out, rows, D, dtype):
     _dev(ids, "embed ids")
-    _check(load().mmrca_embed_fwd(ptr(ids), ptr(pos_ids), ptr(word), ptr(pos), ptr(type_row), ptr(out), rows, D, dtype, stream_ptr()), "mmrca_embed_fwd")
+    _launch("mmrca_embed_fwd", ptr(ids), ptr(pos_ids), ptr(word), ptr(pos), ptr(type_row), ptr(out), rows, D, dtype)
 
 
 def embed_bwd(dout, ids, pos_ids, dword, dpos, dtype_row, rows, D, dtype, pad_id=-1, pos_pad_id=-1):
-    _check(load().mmrca_embed_bwd(ptr(dout), ptr(ids), ptr(pos_ids), ptr(dword), ptr(dpos), ptr(dtype_row), rows, D,
-                                  pad_id, pos_pad_id, dtype, stream_ptr()), "mmrca_embed_bwd")
+    _launch("mmrca_embed_bwd", ptr(dout), ptr(ids), ptr(pos_ids), ptr(dword), ptr(dpos), ptr(dtype_row), rows, D, pad_id, pos_pad_id, dtype)
 
 
 def patchify_fwd(images, patches, B, Cc, Himg, Wimg, P, dtype):
     _dev(images, "patchify images")
-    _check(load().mmrca_patchify_fwd(ptr(images), ptr(patches), B, Cc, Himg, Wimg, P, dtype, stream_ptr()), "mmrca_patchify_fwd")
+    _launch("mmrca_patchify_fwd", ptr(images), ptr(patches), B, Cc, Himg, Wimg, P, dtype)
 
 
 def vit_assemble_fwd(proj, cls, pos, x, B, nP, D, dtype):
-    _check(load().mmrca_vit_assemble_fwd(ptr(proj), ptr(cls), ptr(pos), ptr(x), B, nP, D, dtype, stream_ptr()), "mmrca_vit_assemble_fwd")
+    _launch("mmrca_vit_assemble_fwd", ptr(proj), ptr(cls), ptr(pos), ptr(x), B, nP, D, dtype)
 
 
 def vit_assemble_bwd(dx, dproj, dcls, dpos, B, nP, D, dtype):
-    _check(load().mmrca_vit_assemble_bwd(ptr(dx), ptr(dproj), ptr(dcls), ptr(dpos), B, nP, D, dtype, stream_ptr()), "mmrca_vit_assemble_bwd")
+    _launch("mmrca_vit_assemble_bwd", ptr(dx), ptr(dproj), ptr(dcls), ptr(dpos), B, nP, D, dtype)
 
 
 def head_fwd(img, txt, w: HeadPtrs, logits, B, d_img, d_txt, n_classes, reverse, mode, drop_p, seed, dtype):
     _dev(img, "head img")
     with _Bracket("head_fwd", (B, d_img, d_txt)):
-        _check(load().mmrca_head_fwd(ptr(img), ptr(txt), C.byref(w), ptr(logits), B, d_img, d_txt, n_classes, int(reverse), mode,
-                                     drop_p, seed, dtype, stream_ptr()), "mmrca_head_fwd")
+        _launch("mmrca_head_fwd", ptr(img), ptr(txt), C.byref(w), ptr(logits), B, d_img, d_txt, n_classes, int(reverse), mode, drop_p, seed, dtype)
 
 
 _HEAD_WS = {}      # (device index, stream) -> workspace tensor of the head backward (grows on demand)
 
 
 def head_bwd_workspace_bytes(B, d_img, d_txt) -> int:
-    fn = load().mmrca_head_bwd_workspace_bytes
-    fn.restype, fn.argtypes = C.c_int64, [_i32, _i32, _i32]
-    return int(fn(B, d_img, d_txt))
+    return int(load().mmrca_head_bwd_workspace_bytes(B, d_img, d_txt))
 
 
 def head_bwd(dlogits, img, txt, w: HeadPtrs, g: HeadPtrs, dimg, dtxt, B, d_img, d_txt, n_classes, reverse, mode, drop_p, seed, dtype,
@@ -574,48 +460,45 @@ def head_bwd(dlogits, img, txt, w: HeadPtrs, g: HeadPtrs, dimg, dtxt, B, d_img, 
         if workspace is None or workspace.numel() < need:
             workspace = _HEAD_WS[key] = torch.empty(need, dtype=torch.uint8, device=img.device)
     with _Bracket("head_bwd", (B, d_img, d_txt)):
-        _check(load().mmrca_head_bwd(ptr(dlogits), ptr(img), ptr(txt), C.byref(w), C.byref(g), ptr(dimg), ptr(dtxt), B, d_img, d_txt,
-                                     n_classes, int(reverse), mode, drop_p, seed, dtype, ptr(workspace),
-                                     workspace.numel() * workspace.element_size(), stream_ptr()), "mmrca_head_bwd")
+        _launch("mmrca_head_bwd", ptr(dlogits), ptr(img), ptr(txt), C.byref(w), C.byref(g), ptr(dimg), ptr(dtxt), B, d_img, d_txt, n_classes,
+                int(reverse), mode, drop_p, seed, dtype, ptr(workspace), workspace.numel() * workspace.element_size())
 
 
 def linear_cls_fwd(feat, ld, W, b, logits, B, F, Cc, drop_p, seed, dtype):
     """logits [B,C] fp32 = (feat * keep / (1 - drop_p)) W^T + b; feat rows of stride ``ld`` (elements) in ``dtype``"""
     _dev(feat, "linear_cls feat")
     with _Bracket("linear_cls_fwd", (B, F, Cc)):
-        _check(load().mmrca_linear_cls_fwd(ptr(feat), ld, ptr(W), ptr(b), ptr(logits), B, F, Cc, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                           dtype, stream_ptr()), "mmrca_linear_cls_fwd")
+        _launch("mmrca_linear_cls_fwd", ptr(feat), ld, ptr(W), ptr(b), ptr(logits), B, F, Cc, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, dtype)
 
 
 def linear_cls_bwd(dlogits, feat, ld, W, dW, db, dfeat, B, F, Cc, drop_p, seed, dtype):
     """dW / db are ACCUMULATED (fixed-order reduction over B, no atomics); dfeat (optional) [B, F] in ``dtype`` with the forward's mask"""
     _dev(dlogits, "linear_cls dlogits")
     with _Bracket("linear_cls_bwd", (B, F, Cc)):
-        _check(load().mmrca_linear_cls_bwd(ptr(dlogits), ptr(feat), ld, ptr(W), ptr(dW), ptr(db), ptr(dfeat), B, F, Cc, float(drop_p),
-                                           int(seed) & 0xFFFFFFFFFFFFFFFF, dtype, stream_ptr()), "mmrca_linear_cls_bwd")
+        _launch("mmrca_linear_cls_bwd", ptr(dlogits), ptr(feat), ld, ptr(W), ptr(dW), ptr(db), ptr(dfeat), B, F, Cc, float(drop_p),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, dtype)
 
 
 def xent_fwd_bwd(logits, labels, class_w, smoothing, loss, dlogits, B, Cc, grad_scale=1.0):
     _dev(logits, "xent logits")
-    _check(load().mmrca_xent_fwd_bwd(ptr(logits), ptr(labels), ptr(class_w), smoothing, ptr(loss), ptr(dlogits), B, Cc, grad_scale, stream_ptr()), "mmrca_xent_fwd_bwd")
+    _launch("mmrca_xent_fwd_bwd", ptr(logits), ptr(labels), ptr(class_w), smoothing, ptr(loss), ptr(dlogits), B, Cc, grad_scale)
 
 
 def sgd_step(p, g, lp, n, lr, wd, grad_scale=1.0, lp_lo=None):
     """lp / lp_lo: bf16 working copy (hi plane) and, in bf16x3 mode, the lo plane, rewritten in the same pass"""
     _dev(p, "sgd params")
     if lp_lo is not None:
-        _check(load().mmrca_sgd_step_x3(ptr(p), ptr(g), ptr(lp), ptr(lp_lo), n, lr, wd, grad_scale, stream_ptr()), "mmrca_sgd_step_x3")
+        _launch("mmrca_sgd_step_x3", ptr(p), ptr(g), ptr(lp), ptr(lp_lo), n, lr, wd, grad_scale)
         return
-    _check(load().mmrca_sgd_step(ptr(p), ptr(g), ptr(lp), n, lr, wd, grad_scale, stream_ptr()), "mmrca_sgd_step")
+    _launch("mmrca_sgd_step", ptr(p), ptr(g), ptr(lp), n, lr, wd, grad_scale)
 
 
 def adamw_step(p, g, m, v, lp, n, lr, b1, b2, eps, wd, step, grad_scale=1.0, lp_lo=None):
     _dev(p, "adamw params")
     if lp_lo is not None:
-        _check(load().mmrca_adamw_step_x3(ptr(p), ptr(g), ptr(m), ptr(v), ptr(lp), ptr(lp_lo), n, lr, b1, b2, eps, wd, step, grad_scale,
-                                          stream_ptr()), "mmrca_adamw_step_x3")
+        _launch("mmrca_adamw_step_x3", ptr(p), ptr(g), ptr(m), ptr(v), ptr(lp), ptr(lp_lo), n, lr, b1, b2, eps, wd, step, grad_scale)
         return
-    _check(load().mmrca_adamw_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(lp), n, lr, b1, b2, eps, wd, step, grad_scale, stream_ptr()), "mmrca_adamw_step")
+    _launch("mmrca_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(lp), n, lr, b1, b2, eps, wd, step, grad_scale)
 
 
 SEED_EPOCH_STRIDE = 1000003      # = MMRCA_SEED_EPOCH_STRIDE (csrc/common.h) = the per-step stride of engine._site_seed
@@ -629,14 +512,14 @@ def hier_pool_fwd(x, out, ld_out, B, H, W, Cc, k, dtype):
     window of a wider [B, ld_out] buffer)"""
     _dev(x, "hier_pool x")
     with _Bracket("hier_pool_fwd", (B, H, W, Cc, k)):
-        _check(load().mmrca_hier_pool_fwd(ptr(x), ptr(out), ld_out, B, H, W, Cc, k, dtype, stream_ptr()), "mmrca_hier_pool_fwd")
+        _launch("mmrca_hier_pool_fwd", ptr(x), ptr(out), ld_out, B, H, W, Cc, k, dtype)
 
 
 def hier_pool_bwd(d, ld_d, dx, B, H, W, Cc, k, dtype):
     """dx [B*H*W, C] += d / k^2 at the pixels the windows cover"""
     _dev(dx, "hier_pool dx")
     with _Bracket("hier_pool_bwd", (B, H, W, Cc, k)):
-        _check(load().mmrca_hier_pool_bwd(ptr(d), ld_d, ptr(dx), B, H, W, Cc, k, dtype, stream_ptr()), "mmrca_hier_pool_bwd")
+        _launch("mmrca_hier_pool_bwd", ptr(d), ld_d, ptr(dx), B, H, W, Cc, k, dtype)
 
 
 def _seg_array(seg_off):
@@ -647,15 +530,15 @@ def hier_norm_fwd(raw, x, inv, B, ld, seg_off, nseg_a, drop_p, seed_a, seed_b):
     """per-segment L2 normalisation + dropout (group a = the first nseg_a segments, group b the rest; one mask seed each)"""
     _dev(raw, "hier_norm raw")
     with _Bracket("hier_norm_fwd", (B, ld)):
-        _check(load().mmrca_hier_norm_fwd(ptr(raw), ptr(x), ptr(inv), B, ld, _seg_array(seg_off), len(seg_off) - 1, nseg_a, float(drop_p),
-                                          _u64v(seed_a), _u64v(seed_b), stream_ptr()), "mmrca_hier_norm_fwd")
+        _launch("mmrca_hier_norm_fwd", ptr(raw), ptr(x), ptr(inv), B, ld, _seg_array(seg_off), len(seg_off) - 1, nseg_a, float(drop_p), _u64v(seed_a),
+                _u64v(seed_b))
 
 
 def hier_norm_bwd(dx, raw, inv, draw, B, ld, seg_off, nseg_a, drop_p, seed_a, seed_b):
     _dev(dx, "hier_norm dx")
     with _Bracket("hier_norm_bwd", (B, ld)):
-        _check(load().mmrca_hier_norm_bwd(ptr(dx), ptr(raw), ptr(inv), ptr(draw), B, ld, _seg_array(seg_off), len(seg_off) - 1, nseg_a,
-                                          float(drop_p), _u64v(seed_a), _u64v(seed_b), stream_ptr()), "mmrca_hier_norm_bwd")
+        _launch("mmrca_hier_norm_bwd", ptr(dx), ptr(raw), ptr(inv), ptr(draw), B, ld, _seg_array(seg_off), len(seg_off) - 1, nseg_a, float(drop_p),
+                _u64v(seed_a), _u64v(seed_b))
 
 
 def hier_linear_workspace_bytes(B, N, K) -> int:
@@ -666,17 +549,15 @@ def hier_linear_relu_fwd(X, ldx, W, b, Y, ldy, ws, B, N, K):
     """Y = relu(X W^T + b) with the contraction split over the chip; ws: a uint8 / fp32 workspace of hier_linear_workspace_bytes"""
     _dev(X, "hier_linear X")
     with _Bracket("hier_linear_relu_fwd", (B, N, K)):
-        _check(load().mmrca_hier_linear_relu_fwd(ptr(X), ldx, ptr(W), ptr(b), ptr(Y), ldy, ptr(ws), ws.numel() * ws.element_size(), B, N, K,
-                                                 stream_ptr()), "mmrca_hier_linear_relu_fwd")
+        _launch("mmrca_hier_linear_relu_fwd", ptr(X), ldx, ptr(W), ptr(b), ptr(Y), ldy, ptr(ws), ws.numel() * ws.element_size(), B, N, K)
 
 
 def hier_linear_relu_bwd(dY, lddy, Y, ldy, X, ldx, W, dW, db, dX, lddx, ws, B, N, K):
     """dW += dZ^T X, db += colsum(dZ), dX (or None) = dZ W with dZ = dY * (Y > 0); ws: as in the forward (None is fine without dX)"""
     _dev(dY, "hier_linear dY")
     with _Bracket("hier_linear_relu_bwd", (B, N, K)):
-        _check(load().mmrca_hier_linear_relu_bwd(ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, ptr(ws),
-                                                 0 if ws is None else ws.numel() * ws.element_size(), B, N, K, stream_ptr()),
-               "mmrca_hier_linear_relu_bwd")
+        _launch("mmrca_hier_linear_relu_bwd", ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, ptr(ws),
+                0 if ws is None else ws.numel() * ws.element_size(), B, N, K)
 
 
 # ---- head of the bimodal GRU late-fusion model (csrc/gru.hip) ---------------------------------------------------------------
@@ -684,15 +565,14 @@ def gru_linear_fwd(X, ldx, W, b, Y, ldy, B, N, K, relu=False):
     """Y [B, N] = X W^T + b (then ReLU); fp32, row pitches in elements"""
     _dev(X, "gru_linear X")
     with _Bracket("gru_linear_fwd", (B, N, K)):
-        _check(load().mmrca_gru_linear_fwd(ptr(X), ldx, ptr(W), ptr(b), ptr(Y), ldy, B, N, K, int(bool(relu)), stream_ptr()), "mmrca_gru_linear_fwd")
+        _launch("mmrca_gru_linear_fwd", ptr(X), ldx, ptr(W), ptr(b), ptr(Y), ldy, B, N, K, int(bool(relu)))
 
 
 def gru_linear_bwd(dY, lddy, Y, ldy, X, ldx, W, dW, db, dX, lddx, B, N, K):
     """dW += dZ^T X, db += colsum(dZ), dX = dZ W with dZ = dY (* (Y > 0) when Y is given); dW / db / dX are each optional"""
     _dev(dY, "gru_linear dY")
     with _Bracket("gru_linear_bwd", (B, N, K)):
-        _check(load().mmrca_gru_linear_bwd(ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, B, N, K, stream_ptr()),
-               "mmrca_gru_linear_bwd")
+        _launch("mmrca_gru_linear_bwd", ptr(dY), lddy, ptr(Y), ldy, ptr(X), ldx, ptr(W), ptr(dW), ptr(db), ptr(dX), lddx, B, N, K)
 
 
 def _ptr_table(tensors, name):
@@ -713,7 +593,7 @@ def gru_fwd(gi, whh, bhh, hseq, gates, hn, T, H):
         if g.numel() < T * 3 * H or a.numel() < T * 3 * H or s.numel() < (T + 1) * H or h.numel() < T * H:
             raise MmrcaError(f"gru_fwd: a buffer is smaller than T={T}, H={H} need")
     with _Bracket("gru_fwd", (n, T, H)):
-        _check(load().mmrca_gru_fwd(n, *[_ptr_table(v, "gru_fwd") for v in (gi, whh, bhh, hseq, gates, hn)], T, H, stream_ptr()), "mmrca_gru_fwd")
+        _launch("mmrca_gru_fwd", n, *[_ptr_table(v, "gru_fwd") for v in (gi, whh, bhh, hseq, gates, hn)], T, H)
 
 
 def gru_bwd(whh, hseq, gates, hn, dout, lddout, carry, dgi, dgh, T, H):
@@ -727,27 +607,27 @@ def gru_bwd(whh, hseq, gates, hn, dout, lddout, carry, dgi, dgh, T, H):
             raise MmrcaError(f"gru_bwd: a buffer is smaller than T={T}, H={H} need")
     lds = (C.c_int * n)(*[int(v) for v in lddout])
     with _Bracket("gru_bwd", (n, T, H)):
-        _check(load().mmrca_gru_bwd(n, *[_ptr_table(v, "gru_bwd") for v in (whh, hseq, gates, hn, dout)], lds,
-                                    *[_ptr_table(v, "gru_bwd") for v in (carry, dgi, dgh)], T, H, stream_ptr()), "mmrca_gru_bwd")
+        _launch("mmrca_gru_bwd", n, *[_ptr_table(v, "gru_bwd") for v in (whh, hseq, gates, hn, dout)], lds,
+                *[_ptr_table(v, "gru_bwd") for v in (carry, dgi, dgh)], T, H)
 
 
 def hadamard_fwd(a, lda, x2, ldb, k1, k2, bias, out, ldo, B, Cc):
     """out = tanh(a * k1 + x2 * k2 + bias) over [B, Cc]"""
     _dev(a, "hadamard a")
-    _check(load().mmrca_hadamard_fwd(ptr(a), lda, ptr(x2), ldb, ptr(k1), ptr(k2), ptr(bias), ptr(out), ldo, B, Cc, stream_ptr()), "mmrca_hadamard_fwd")
+    _launch("mmrca_hadamard_fwd", ptr(a), lda, ptr(x2), ldb, ptr(k1), ptr(k2), ptr(bias), ptr(out), ldo, B, Cc)
 
 
 def hadamard_bwd(d1, ld1, d2, ld2, a, lda, x2, ldb, out, ldo, k1, k2, da, ldda, db, lddb, dk1, dk2, dbias, B, Cc):
     """d = (d1 + d2) (1 - out^2): da = d k1, db = d k2; dk1 / dk2 / dbias accumulate.  d2 may be None"""
     _dev(d1, "hadamard d1")
-    _check(load().mmrca_hadamard_bwd(ptr(d1), ld1, ptr(d2), ld2, ptr(a), lda, ptr(x2), ldb, ptr(out), ldo, ptr(k1), ptr(k2), ptr(da), ldda,
-                                     ptr(db), lddb, ptr(dk1), ptr(dk2), ptr(dbias), B, Cc, stream_ptr()), "mmrca_hadamard_bwd")
+    _launch("mmrca_hadamard_bwd", ptr(d1), ld1, ptr(d2), ld2, ptr(a), lda, ptr(x2), ldb, ptr(out), ldo, ptr(k1), ptr(k2), ptr(da), ldda, ptr(db),
+            lddb, ptr(dk1), ptr(dk2), ptr(dbias), B, Cc)
 
 
 def dropout_f32(x, ldx, y, ldy, B, Cc, drop_p, seed):
     """y = x * keep / (1 - drop_p) with the counter-based mask of (seed, b * Cc + c); the backward is the same call on the gradient"""
     _dev(x, "dropout x")
-    _check(load().mmrca_dropout_f32(ptr(x), ldx, ptr(y), ldy, B, Cc, float(drop_p), _u64v(seed), stream_ptr()), "mmrca_dropout_f32")
+    _launch("mmrca_dropout_f32", ptr(x), ldx, ptr(y), ldy, B, Cc, float(drop_p), _u64v(seed))
 
 
 _seed_epoch = 0                  # host view of the device-side mask epoch (0 = eager launches draw the seeds they are given)
@@ -761,7 +641,7 @@ def seed_epoch_set(value: int = 0, device_value: Optional[torch.Tensor] = None):
         _dev(device_value, "seed_epoch_set")
         if device_value.dtype != torch.int64 or device_value.numel() < 1:
             raise MmrcaError("seed_epoch_set: device_value must be an int64 tensor")
-    _check(load().mmrca_seed_epoch_set(ptr(device_value), int(value) & 0xFFFFFFFFFFFFFFFF, stream_ptr()), "mmrca_seed_epoch_set")
+    _launch("mmrca_seed_epoch_set", ptr(device_value), int(value) & 0xFFFFFFFFFFFFFFFF)
     _seed_epoch = None if device_value is not None else int(value)
 
 
@@ -770,7 +650,7 @@ def sd_rowscale(p: torch.Tensor, out: torch.Tensor, n: int, B: int, seed: int):
     _dev(p, "sd_rowscale"); _dev(out, "sd_rowscale")
     if p.dtype != torch.float32 or out.dtype != torch.float32 or p.numel() < n or out.numel() < n * B:
         raise MmrcaError("sd_rowscale: p [n] and out [n, B] must be fp32 tensors of at least those sizes")
-    _check(load().mmrca_sd_rowscale(ptr(p), ptr(out), int(n), int(B), int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ptr()), "mmrca_sd_rowscale")
+    _launch("mmrca_sd_rowscale", ptr(p), ptr(out), int(n), int(B), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
 def seed_epoch_host():
@@ -785,7 +665,7 @@ def seed_epoch_note(value):
 
 def cast_f32_to_bf16(src, dst, n):
     _dev(src, "cast src")
-    _check(load().mmrca_cast_f32_to_bf16(ptr(src), ptr(dst), n, stream_ptr()), "mmrca_cast_f32_to_bf16")
+    _launch("mmrca_cast_f32_to_bf16", ptr(src), ptr(dst), n)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -864,32 +744,22 @@ _CONV_BYTES = {
 }
 
 
-_PARAM_NAMES = {}      # entry point -> parameter names of its prototype in include/mmrca.h; read at the first profiled launch
-
-
 def _named(name, args):
-    """the arguments of one launch under the header's parameter names (profiled launches only: the header is not read otherwise)"""
-    from types import SimpleNamespace
-    if not _PARAM_NAMES:
-        from . import abi
-        try:
-            protos = abi.prototypes()
-        except abi.MmrcaError as e:
-            raise MmrcaError(str(e)) from None
-        _PARAM_NAMES.update({fn: [pname for _, pname in params] for fn, (_, params) in protos.items()})
-    return SimpleNamespace(**dict(zip(_PARAM_NAMES[name], args)))
+    """the arguments of one launch under the header's parameter names (profiled launches only)"""
+    return SimpleNamespace(**dict(zip((pname for _, pname in _prototypes()[name][1]), args)))
 
 
 def _c(name, *args):
-    if CONV_PROFILE is not None:
-        fam, fn = _CONV_BYTES.get(name, ("other", lambda a: 0))
-        named = _named(name, args)
-        e0, e1 = _events()
-        _check(getattr(load(), name)(*args, stream_ptr()), name)
-        e1.record()
-        CONV_PROFILE.append((fam, int(fn(named)), e0, e1))
+    """_launch of a conv-path entry point, bracketed by events and counted in bytes while bench.py's CONV_PROFILE is on"""
+    if CONV_PROFILE is None:
+        _launch(name, *args)
         return
-    _check(getattr(load(), name)(*args, stream_ptr()), name)
+    fam, fn = _CONV_BYTES.get(name, ("other", lambda a: 0))
+    named = _named(name, args)
+    e0, e1 = _events()
+    _launch(name, *args)
+    e1.record()
+    CONV_PROFILE.append((fam, int(fn(named)), e0, e1))
 
 
 def nchw_to_rows(images, x, B, C, H, W, dtype):
@@ -1107,8 +977,7 @@ def channel_gather(inp, cmap, out, rows, Cin, Cout, ld_out, col0, dtype):
 def nonorm_fwd(x, res, gamma, beta, sum_out, y, rows, D, ld_x, ld_res, ld_sum, ld_y, dtype):
     """s = x (+ res), y = s * gamma + beta on [rows, D]; sum_out (optional, may be x) receives s"""
     _dev(x, "nonorm_fwd x")
-    _check(load().mmrca_nonorm_fwd(ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), rows, D, ld_x, ld_res, ld_sum, ld_y,
-                                   dtype, stream_ptr()), "mmrca_nonorm_fwd")
+    _launch("mmrca_nonorm_fwd", ptr(x), ptr(res), ptr(gamma), ptr(beta), ptr(sum_out), ptr(y), rows, D, ld_x, ld_res, ld_sum, ld_y, dtype)
 
 
 def nonorm_bwd_workspace_bytes(rows, D) -> int:
@@ -1118,19 +987,16 @@ def nonorm_bwd_workspace_bytes(rows, D) -> int:
 def nonorm_bwd(dy, s, gamma, dres, ds_out, dgamma, dbeta, dbias, ws, rows, D, ld_dy, ld_s, ld_dres, ld_ds, dtype):
     """ds_out = dy * gamma (+ dres); dgamma += sum dy * s, dbeta += sum dy, dbias (optional) += gamma * sum dy; ws: workspace tensor"""
     _dev(dy, "nonorm_bwd dy")
-    _check(load().mmrca_nonorm_bwd(ptr(dy), ptr(s), ptr(gamma), ptr(dres), ptr(ds_out), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(ws),
-                                   ws.numel() * ws.element_size(), rows, D, ld_dy, ld_s, ld_dres, ld_ds, dtype, stream_ptr()),
-           "mmrca_nonorm_bwd")
+    _launch("mmrca_nonorm_bwd", ptr(dy), ptr(s), ptr(gamma), ptr(dres), ptr(ds_out), ptr(dgamma), ptr(dbeta), ptr(dbias), ptr(ws),
+            ws.numel() * ws.element_size(), rows, D, ld_dy, ld_s, ld_dres, ld_ds, dtype)
 
 
 def trigram_embed_fwd(ids, perm, word, out, M, B, T, E, vocab, dtype):
     """ids int32 [B, T] (padded), perm int32 [M] or None, word [vocab, E] -> out [M, 3E] = word[next] | word[id] | word[prev]"""
     _dev(ids, "trigram_embed_fwd ids")
-    _check(load().mmrca_trigram_embed_fwd(ptr(ids), ptr(perm), ptr(word), ptr(out), M, B, T, E, vocab, dtype, stream_ptr()),
-           "mmrca_trigram_embed_fwd")
+    _launch("mmrca_trigram_embed_fwd", ptr(ids), ptr(perm), ptr(word), ptr(out), M, B, T, E, vocab, dtype)
 
 
 def trigram_embed_bwd(dout, ids, perm, dword, M, B, T, E, vocab, pad_id, dtype):
     _dev(dout, "trigram_embed_bwd dout")
-    _check(load().mmrca_trigram_embed_bwd(ptr(dout), ptr(ids), ptr(perm), ptr(dword), M, B, T, E, vocab, pad_id, dtype, stream_ptr()),
-           "mmrca_trigram_embed_bwd")
+    _launch("mmrca_trigram_embed_bwd", ptr(dout), ptr(ids), ptr(perm), ptr(dword), M, B, T, E, vocab, pad_id, dtype)

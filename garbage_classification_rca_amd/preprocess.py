@@ -337,8 +337,7 @@ class GpuImagePipeline:
         main_image.py:412-417)."""
         k, B, _, _ = self._stage(images, pad=pad)
         sums = torch.empty(B, 3, 2, dtype=torch.int64, device=self.device)     # (every sum is far below 2^63: uint64 read as int64)
-        L._check(L.load().mmrca_image_stats_u8(L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(sums), B, self.out_h, self.out_w,
-                                               L.stream_ptr()), "mmrca_image_stats_u8")
+        L._launch("mmrca_image_stats_u8", L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(sums), B, self.out_h, self.out_w)
         self._release(k)
         return sums
 
@@ -348,18 +347,14 @@ class GpuImagePipeline:
         flips in one launch).  aug: one ``sample_train_params`` dict per image -> the full TRAIN_PIPELINE."""
         k, B, nr, any_rot = self._stage(images, flips, aug)
         out = torch.empty(B, 3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
-        lib = L.load()
         mean, std = C.cast(self._mean, C.c_void_p), C.cast(self._std, C.c_void_p)
         if aug is None:
-            L._check(lib.mmrca_image_preprocess(L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(out), B, self.out_h, self.out_w,
-                                                mean, std, L.stream_ptr()), "mmrca_image_preprocess")
+            L._launch("mmrca_image_preprocess", L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(out), B, self.out_h, self.out_w, mean, std)
         else:
             if any_rot:
-                L._check(lib.mmrca_image_rotate_crop(L.ptr(self._dev[k]), L.ptr(self._dev_aug[k]), B, self.max_pixels, L.stream_ptr()),
-                         "mmrca_image_rotate_crop")
-            L._check(lib.mmrca_image_resize_u8(L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(self._u8[0]), B, self.out_h,
-                                               self.out_w, L.stream_ptr()), "mmrca_image_resize_u8")
-            L._check(lib.mmrca_image_augment(L.ptr(self._u8[0]), L.ptr(self._u8[1]), self._dev_aug[k].data_ptr() + nr, L.ptr(out), B,
-                                             self.out_h, self.out_w, mean, std, L.stream_ptr()), "mmrca_image_augment")
+                L._launch("mmrca_image_rotate_crop", L.ptr(self._dev[k]), L.ptr(self._dev_aug[k]), B, self.max_pixels)
+            L._launch("mmrca_image_resize_u8", L.ptr(self._dev[k]), L.ptr(self._dev_desc[k]), L.ptr(self._u8[0]), B, self.out_h, self.out_w)
+            L._launch("mmrca_image_augment", L.ptr(self._u8[0]), L.ptr(self._u8[1]), self._dev_aug[k].data_ptr() + nr, L.ptr(out), B,
+                      self.out_h, self.out_w, mean, std)
         self._release(k)
         return out

@@ -1,5 +1,5 @@
 """The bf16x3 attention forward at 225 <= S <= 512 (mha_fwd_x3_c_k, csrc/attention_mfma.hip), the part that needs no GPU: the range
-lib.py announces to the engines, and that the C ABI did not grow for it (the same entry point, the same prototype, the same table)."""
+lib.py announces to the engines, and that the C ABI did not grow for it (the same entry point, the same prototype, the same binding)."""
 import ctypes as C
 import os
 import re
@@ -31,6 +31,7 @@ def test_the_entry_point_keeps_its_prototype_and_the_table_its_size():
     assert names == [n for n, _ in X3_PARAMS]
     restype, params = abi.prototypes(HEADER, {"MmrcaHeadWeights": C.POINTER(L.HeadPtrs), "MmrcaHeadGrads": C.POINTER(L.HeadPtrs)})["mmrca_mha_fwd_x3"]
     assert restype is C.c_int
-    assert [ctype for ctype, _ in params] == [t for _, t in X3_PARAMS] == list(L._SIGS["mmrca_mha_fwd_x3"])
-    assert len(L._SIGS) == 105 and len(L.EXPORTS) == len(set(re.findall(r"\b(mmrca_[a-z0-9_]+)\s*\(", text)))
+    assert [ctype for ctype, _ in params] == [t for _, t in X3_PARAMS] == list(L.load().mmrca_mha_fwd_x3.argtypes)
+    assert L.load().mmrca_mha_fwd_x3.restype is C.c_int
+    assert all(getattr(L.load(), name).argtypes is not None for name in set(re.findall(r"\b(mmrca_[a-z0-9_]+)\s*\(", text)))
     assert "1 <= S <= 512" in text[m.start() - 900:m.start()]          # the comment above the prototype names the new range

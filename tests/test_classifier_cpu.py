@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from garbage_classification_rca_amd import classifiers as C
+from garbage_classification_rca_amd import abi
 from garbage_classification_rca_amd import lib as L
 from garbage_classification_rca_amd import main_image as MI
 from garbage_classification_rca_amd import main_text as MT
@@ -113,7 +114,7 @@ def test_library_exports_the_classifier_head():
         L.build_library()
     lib = ctypes.CDLL(L.LIB_PATH)
     for name in ("mmrca_linear_cls_fwd", "mmrca_linear_cls_bwd"):
-        assert hasattr(lib, name) and name in L.EXPORTS
+        assert hasattr(lib, name) and name in abi.prototypes() and getattr(L.load(), name).argtypes is not None
     assert "mmrca_linear_cls_fwd" in open(os.path.join(ROOT, "include", "mmrca.h")).read()
 
 

@@ -33,8 +33,10 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert len(declared) >= 20
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/mmrca.h but not exported"
-    assert declared == set(L.EXPORTS), declared ^ set(L.EXPORTS)
-    assert L.load().mmrca_version() >= 1
+    bound = L.load()
+    for name in declared:
+        assert getattr(bound, name).argtypes is not None, f"{name} declared in include/mmrca.h but not typed by lib.load()"
+    assert bound.mmrca_version() >= 1
 
 
 def test_oracle_architecture_tables_are_independent_and_agree_with_transformers_and_the_product():

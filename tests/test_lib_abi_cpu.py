@@ -1,6 +1,7 @@
 """lib.py against include/mmrca.h as garbage_classification_rca_amd/abi.py reads it: the parser against an independent count, the
-hand-written ctypes table and the Python constants against the header, every wrapper of lib.py against the prototype it calls (a
-recorder stands in for the library: no GPU), and the conv byte table against recorded values.  Needs only the cross-compiled library."""
+types lib.load() gives every declared function and the Python constants against the header, every wrapper of lib.py against the
+prototype it calls (a recorder stands in for the library: no GPU), and the conv byte table against recorded values.  Needs only the
+cross-compiled library."""
 import ctypes as C
 import inspect
 import os
@@ -22,26 +23,24 @@ HEAD_PTR = C.POINTER(L.HeadPtrs)
 STRUCT_POINTERS = {"MmrcaHeadWeights": HEAD_PTR, "MmrcaHeadGrads": HEAD_PTR}
 
 
-def test_parser_finds_every_declared_function_and_the_hand_typed_table_says_what_the_header_says():
+def test_parser_finds_every_declared_function_and_the_loaded_library_is_typed_as_the_header_says():
     declared = set(re.findall(r"\b(mmrca_[a-z0-9_]+)\s*\(", open(HEADER).read()))      # test_host_cpu.py's independent regex
     protos = abi.prototypes(HEADER, STRUCT_POINTERS)
-    assert set(protos) == declared and len(protos) == len(declared) >= 100
-    assert L.EXPORTS == sorted(declared)
-    # lib._SIGS: widths, order and count of every argument, not only the names
-    assert len(L._SIGS) == 105
-    for name, sig in L._SIGS.items():
-        restype, params = protos[name]
-        assert list(sig) == [ctype for ctype, _ in params], name
-        assert restype is C.c_int, name               # load() gives every _SIGS entry restype c_int
-    # ... and what load() types outside the table
+    assert set(protos) == declared and len(protos) == len(declared)
+    assert len(protos) == 117                          # the one count of entry points in the tree
     if not os.path.exists(L.LIB_PATH):
         L.build_library()
     lib = L.load()
-    assert L.head_bwd_workspace_bytes(2, 1280, 768) > 0         # host arithmetic; the wrapper types its function at each call
-    for name in ("mmrca_head_bwd_workspace_bytes", "mmrca_gemm_splitk_workspace_bytes", "mmrca_gemm_streamk_workspace_bytes", "mmrca_hier_linear_workspace_bytes",
-                 "mmrca_nonorm_bwd_workspace_bytes", "mmrca_conv3x3_stat_slots"):
+    # widths, order and count of every argument and the return type, of every declared function
+    for name, (restype, params) in protos.items():
         fn = getattr(lib, name)
-        assert (fn.restype, list(fn.argtypes)) == (protos[name][0], [ctype for ctype, _ in protos[name][1]]), name
+        assert fn.argtypes is not None, name
+        assert (fn.restype, list(fn.argtypes)) == (restype, [ctype for ctype, _ in params]), name
+    # what lib._launch relies on: every entry point that takes a stream takes it last and reports through an int status
+    for name, (restype, params) in protos.items():
+        if "stream" in [pname for _, pname in params]:
+            assert params[-1] == (C.c_void_p, "stream") and restype is C.c_int, name
+    assert L.head_bwd_workspace_bytes(2, 1280, 768) > 0         # host arithmetic
     assert lib.mmrca_last_error.restype is protos["mmrca_last_error"][0] is C.c_char_p and protos["mmrca_last_error"][1] == []
     assert lib.mmrca_version.restype is protos["mmrca_version"][0] is C.c_int
     assert protos["mmrca_head_bwd_workspace_bytes"] == (C.c_int64, [(C.c_int, "B"), (C.c_int, "d_img"), (C.c_int, "d_txt")])
@@ -74,6 +73,18 @@ def test_parser_rejects_what_the_grammar_does_not_cover(tmp_path, fragment, word
 def test_missing_header_is_an_error_that_says_so(tmp_path):
     with pytest.raises(abi.MmrcaError, match="nowhere.h"):
         abi.prototypes(str(tmp_path / "nowhere.h"))
+
+
+def test_bind_names_a_declared_function_the_library_lacks(tmp_path):
+    if not os.path.exists(L.LIB_PATH):
+        L.build_library()
+    path = tmp_path / "ahead.h"
+    path.write_text("int mmrca_version(void);\nint mmrca_not_built_yet(const void* x, int64_t n, void* stream);\n")
+    cdll = C.CDLL(L.LIB_PATH)                           # a handle of its own: lib.load()'s functions keep their types
+    with pytest.raises(abi.MmrcaError, match=r"mmrca_not_built_yet .*rebuild"):
+        abi.bind(cdll, abi.prototypes(str(path)))
+    abi.bind(cdll, {"mmrca_version": abi.prototypes(str(path))["mmrca_version"]})
+    assert (cdll.mmrca_version.restype, list(cdll.mmrca_version.argtypes)) == (C.c_int, []) and cdll.mmrca_version() >= 1
 
 
 # ------------------------------------------------------------------------------------------------ constants
@@ -364,8 +375,8 @@ def test_every_wrapper_marshals_what_the_header_declares(monkeypatch):
     assert public - NOT_A_LAUNCH == called, (public - NOT_A_LAUNCH) ^ called
     assert len(called) == 92
     reached = {name for name, _ in rec.calls}
-    assert reached == set(L.EXPORTS) - NO_WRAPPER, reached ^ (set(L.EXPORTS) - NO_WRAPPER)
-    assert NO_WRAPPER <= set(L.EXPORTS)
+    assert reached == set(protos) - NO_WRAPPER, reached ^ (set(protos) - NO_WRAPPER)
+    assert NO_WRAPPER <= set(protos)
     assert len(L._STREAMK_WS) == 1                                 # the registration went through
 
 

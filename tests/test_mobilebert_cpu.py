@@ -9,6 +9,7 @@ import torch
 
 from garbage_classification_rca_amd import calculate_test_accuracy_text as CT
 from garbage_classification_rca_amd import classifiers as C
+from garbage_classification_rca_amd import abi
 from garbage_classification_rca_amd import lib as L
 from garbage_classification_rca_amd import main_text as MT
 from garbage_classification_rca_amd import spec as S
@@ -133,5 +134,5 @@ def test_header_declares_and_library_exports_the_new_entry_points():
     lib = ctypes.CDLL(L.LIB_PATH)
     for name in NEW_EXPORTS:
         assert name + "(" in header, name
-        assert name in L.EXPORTS, name
+        assert name in abi.prototypes() and getattr(L.load(), name).argtypes is not None, name
         assert hasattr(lib, name), name

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Where a (b, h) of the fused ViT attention backward spends its cycles: s_memtime stamps of wave 0 of every workgroup at entry,
 after the first staging barrier, between the two parts and at exit (diagnostic build path of mha_bwd_fused_mfma_v_k; shares, not run time)."""
-import sys, os, math, ctypes, torch
+import sys, os, math, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from garbage_classification_rca_amd import lib as L
 lib = L.load()
@@ -16,7 +16,7 @@ L.mha_fwd(qkv, None, out, lse, B, H, S, dh, sc, L.BF16)
 for _ in range(3):
     L.mha_bwd(qkv, None, out, dout, lse, dqkv, B, H, S, dh, sc, L.BF16)
 st = torch.zeros(B * H * 4, dtype=torch.int64, device="cuda")
-lib.mmrca_debug_attn_stamps(ctypes.c_void_p(st.data_ptr()))
+lib.mmrca_debug_attn_stamps(st.data_ptr())
 L.mha_bwd(qkv, None, out, dout, lse, dqkv, B, H, S, dh, sc, L.BF16)
 torch.cuda.synchronize()
 lib.mmrca_debug_attn_stamps(None)
